@@ -9,7 +9,13 @@ bordered Cholesky solve + back-substitution + de-scaling + xhat update + sumabs)
 in HBM.  With --gpus N (torchrun, one process per GPU) the observations are sharded by tie point
 and the reduced system is all-reduced over RCCL (strong scaling of the same scene).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`).
+--dump-outputs DIR then writes what the last timed step left, the vector of unknowns a caller of the
+step reads back (fba_get_xhat), as DIR/xhat.npy (float64).  The scene is seeded, so the same arguments
+give the same inputs in every run and two builds can be compared output for output.  --full adds what
+takes runs of its own: the per-phase breakdown, the kernel rooflines and the CPU baseline.
 """
 import argparse
 import json
@@ -135,12 +141,19 @@ def main():
     ap.add_argument("--network", default="grid", choices=("grid", "convergent"))
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu", action="store_true")
+    # everything besides the headline figure: the per-phase breakdown and the kernel rooflines (extra
+    # steps after the timed region) and the CPU baseline (host runs of --cpu-seconds; not with --no-cpu)
+    ap.add_argument("--full", action="store_true")
+    # DIR/xhat.npy: xhat after the last timed step (float64, u values: 1.2 MB at config 4, 4.9 MB at 5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     ap.add_argument("--verbose", action="store_true")
     # N > 1: "replicated" = observations sharded, the summed reduced system factored on every rank (the
     # north star's all-reduce of A'PA / A'Pw); "subtree" = the elimination tree's subtrees factored by the
     # ranks that own their tie points, only the top blocks all-reduced (fba_options.split)
     ap.add_argument("--solve", default=os.environ.get("FBA_BENCH_SOLVE", "replicated"), choices=("replicated", "subtree"))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -192,6 +205,54 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
 
+    if world > 1:
+        import torch.distributed as dist
+        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        dt = float(tt.item())
+
+    # what the last timed step left (before --full's extra steps move it on): each rank's own entries,
+    # summed over the ranks to the whole vector
+    xhat_last = None
+    if args.dump_outputs:
+        xhat_last = ctx.get_xhat(owned_only=world > 1)
+        if world > 1:
+            xt = torch.from_numpy(xhat_last).to(dev)
+            dist.all_reduce(xt)
+            xhat_last = xt.cpu().numpy()
+
+    value = args.steps / dt
+    out = {
+        "metric": "Gauss-Newton iter/sec (BuildAwG+solve) and image-point obs/sec",
+        "value": value, "unit": "iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"synthetic fish-eye config {args.config}"
+                               f"{'' if args.network == 'grid' else ' (' + args.network + ' network)'}: {ds.numImg} "
+                               f"images x {ds.numtie} tie points, {ds.n_pts} image points, inner constraints, nK=5",
+                   "n_pts": ds.n_pts, "n_img": ds.numImg, "n_tie": ds.numtie, "u": int(ctx.u),
+                   "parallelism": f"{'subtree-split' if ctx.split else 'obs-shard'}{world}"},
+        "obs_per_s": ds.n_pts * value,
+        "deltasum_last": dsum[-1],
+    }
+    t = None
+    if args.full:
+        t = full_gpu_report(args, ctx, step, ds, out)
+    ctx.close()
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
+        cpu_report(args, folder, ds, t, out)
+    if xhat_last is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "xhat.npy"), xhat_last)
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_gpu_report(args, ctx, step, ds, out):
+    """--full, on the device after the timed region: the per-phase breakdown and the kernel rooflines
+    into `out`; returns the per-step phase times (ms)."""
     # per-phase breakdown, outside the timed region: the same steps with HIP events between the phases
     # (eager launches: the timed loop above replays the captured iteration graphs)
     ctx.set_timing(True)
@@ -201,11 +262,6 @@ def main():
         step()
         phases += ctx.timings()
     ctx.set_timing(False)
-    if world > 1:
-        import torch.distributed as dist
-        tt = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
 
     names = ["linearize", "point", "accumulate", "border", "cholesky", "backward", "update", "total"]
     ms = {n: float(v) for n, v in zip(names, phases)}
@@ -254,46 +310,33 @@ def main():
     # (no dense-equivalent Cholesky rate: u_c^3/3 over the block-sparse factor's time measures the
     # ordering's sparsity, not the kernel, and exceeds the hardware peak)
     phase_roof = {"linearize_accumulate_GBs": lin_bytes / ((t["linearize"] + t["accumulate"]) * 1e-3) / 1e9}
-    value = args.steps / dt
-    out = {
-        "metric": "Gauss-Newton iter/sec (BuildAwG+solve) and image-point obs/sec",
-        "value": value, "unit": "iter/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"synthetic fish-eye config {args.config}"
-                               f"{'' if args.network == 'grid' else ' (' + args.network + ' network)'}: {ds.numImg} "
-                               f"images x {ds.numtie} tie points, {ds.n_pts} image points, inner constraints, nK=5",
-                   "n_pts": ds.n_pts, "n_img": ds.numImg, "n_tie": ds.numtie, "u": int(ctx.u),
-                   "parallelism": f"{'subtree-split' if ctx.split else 'obs-shard'}{world}"},
-        "obs_per_s": ds.n_pts * value,
+    out.update({
         "phase_ms": {k: t[k] for k in names},
-        "deltasum_last": dsum[-1] if dsum else None,
         "roofline": roof,
         **({"roofline_bulk_update": roof_bulk} if roof_bulk else {}),
         "phase_roofline": phase_roof,
-    }
-    ctx.close()
-    if rank == 0 and world == 1 and not args.no_cpu:
-        out["cpu_baseline"], dense = cpu_baseline(folder, args.cpu_seconds)
-        if dense:
-            out["cpu_baseline_dense"] = dense
-        cb = out["cpu_baseline"]
-        if cb.get("value"):
-            # how to read the GPU/CPU ratio: per phase, like for like (the CPU's linearise + per-point
-            # Schur costs ~cores x its ms per point; the factorisations run on the same block pattern)
-            lin_gpu = t["linearize"] + t["point"] + t["accumulate"]
-            lin_cpu = cb["phase_ms"]["linearize_reduce"]
-            out["gpu_vs_cpu"] = {
-                "iteration": value / cb["value"],
-                "linearise_reduce": lin_cpu / lin_gpu if lin_gpu > 0 else None,
-                "factor": cb["solve_ms"]["factor"] / t["cholesky"] if t["cholesky"] > 0 else None,
-                "cpu_linearise_reduce_us_per_point_per_core": 1e3 * lin_cpu * cb["cores"] / ds.n_pts,
-                "gpu_linearise_reduce_ns_per_point": 1e6 * lin_gpu / ds.n_pts}
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+    })
+    return t
+
+
+def cpu_report(args, folder, ds, t, out):
+    """--full, on the host after the context is closed: the CPU baseline and the GPU/CPU ratios into `out`."""
+    value = out["value"]
+    out["cpu_baseline"], dense = cpu_baseline(folder, args.cpu_seconds)
+    if dense:
+        out["cpu_baseline_dense"] = dense
+    cb = out["cpu_baseline"]
+    if cb.get("value"):
+        # how to read the GPU/CPU ratio: per phase, like for like (the CPU's linearise + per-point
+        # Schur costs ~cores x its ms per point; the factorisations run on the same block pattern)
+        lin_gpu = t["linearize"] + t["point"] + t["accumulate"]
+        lin_cpu = cb["phase_ms"]["linearize_reduce"]
+        out["gpu_vs_cpu"] = {
+            "iteration": value / cb["value"],
+            "linearise_reduce": lin_cpu / lin_gpu if lin_gpu > 0 else None,
+            "factor": cb["solve_ms"]["factor"] / t["cholesky"] if t["cholesky"] > 0 else None,
+            "cpu_linearise_reduce_us_per_point_per_core": 1e3 * lin_cpu * cb["cores"] / ds.n_pts,
+            "gpu_linearise_reduce_ns_per_point": 1e6 * lin_gpu / ds.n_pts}
 
 
 if __name__ == "__main__":
