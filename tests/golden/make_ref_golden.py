@@ -16,7 +16,9 @@ BuildRSD.m, sumabs.m.  MATLAB built-ins (readmatrix, inv, mtimes, ...) are resta
 Also (`make_ref_golden.py /root/reference synth_fe`): the same run on conftest.SYNTH_FE, a synthetic
 equidistant fish-eye free network (12 images x 300 tie points, inner constraints, no control, all EOP +
 IOP + 5 radial + 2 decentering) -> ref_synth_fisheye_free.npz; and (`nostd`) cam0 without its Meas_std
-line -> ref_cam0_nostd.json (the reference stops in rmfield at main.m:399).
+line -> ref_cam0_nostd.json (the reference stops in rmfield at main.m:399); and, by name
+(`make_ref_golden.py /root/reference mix_a_noic_pinhole stage2_pinhole`), cam0 under a partial
+Estimate_* mask of tests/flag_masks.py REF_TEXT_VARIANTS -> ref_cam0_<name>.npz.
 
 Only numbers are stored: per-iteration xhat and deltasum, the iteration count, sigma0^2, RMSx / RMSy
 / RMS, v, the numeric RSD columns, dist_scaling, A / w / G of the first BuildAwG call, diag(Cx) after
@@ -37,6 +39,7 @@ sys.path.insert(0, os.path.join(HERE, "..", ".."))
 
 import mlang  # noqa: E402
 from conftest import CAM0_VARIANTS, synth_fe_folder, variant_folder  # noqa: E402
+from flag_masks import REF_TEXT_VARIANTS  # noqa: E402
 
 MAIN_FIRST, MAIN_LAST = 61, 628
 FUNCS = ["ReadFiles", "findSetting", "Buildxhat", "BuildAwG", "BuildRSD", "sumabs"]
@@ -135,7 +138,7 @@ def run_synth(ref_root, root):
 
 def main(ref_root):
     root = tempfile.mkdtemp()
-    only = sys.argv[2:] or sorted(CAM0_VARIANTS) + ["nostd", "synth_fe"]
+    only = sys.argv[2:] or sorted(CAM0_VARIANTS) + sorted(REF_TEXT_VARIANTS) + ["nostd", "synth_fe"]
     if "nostd" in only:
         run_nostd(ref_root, root)
         only = [n for n in only if n != "nostd"]
@@ -143,7 +146,9 @@ def main(ref_root):
         run_synth(ref_root, root)
         only = [n for n in only if n != "synth_fe"]
     for name in only:
-        folder = variant_folder(root, name, CAM0_VARIANTS[name])
+        # a name that is no CAM0_VARIANTS key is a partial Estimate_* mask (tests/flag_masks.py)
+        edits = CAM0_VARIANTS[name] if name in CAM0_VARIANTS else REF_TEXT_VARIANTS[name]
+        folder = variant_folder(root, name, edits)
         t0 = time.time()
         env, awg = run_reference(ref_root, folder)
         out = extract(env, awg)

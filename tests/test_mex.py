@@ -27,9 +27,11 @@ import pytest
 
 from conftest import (ROOT, CAM0_VARIANTS, dist_scaling_of, elem_rel_err, group_rel_err, solver_spread,  # noqa: F401
                       variant_folder)
+from flag_masks import REF_TEXT_VARIANTS
 
 STUB = os.path.join(ROOT, "tests", "mexstub")
 LIBDIR = os.path.join(ROOT, "fish-eye_bundle_adjustment_amd")
+MASKED = REF_TEXT_VARIANTS  # cam0 under mix_a without inner constraints, and under stage2 with them
 DROPINS = ("BuildAwG", "Buildxhat", "BuildRSD")
 
 
@@ -179,10 +181,14 @@ def _rig_folder(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["stage3_pinhole", "stage3_fisheye", "stage1_pinhole", "rig2"])
+@pytest.mark.parametrize("variant", ["stage3_pinhole", "stage3_fisheye", "stage1_pinhole", "rig2",
+                                     "mix_a_noic_pinhole", "stage2_pinhole"])
 def test_mex_dropins_match_oracle(fba, oracle, mexlibs, cam0_folders, tmp_path, variant):
     mx, fns = mexlibs
-    folder = _rig_folder(tmp_path) if variant == "rig2" else cam0_folders[variant]
+    if variant in MASKED:  # cam0 under a partial Estimate_* mask (tests/flag_masks.py)
+        folder = variant_folder(str(tmp_path), variant, MASKED[variant])
+    else:
+        folder = _rig_folder(tmp_path) if variant == "rig2" else cam0_folders[variant]
     od = oracle.load_folder(folder)
     data, EXT, INT, TIE, CNT = data_struct(mx, od)
     # Buildxhat
@@ -192,6 +198,8 @@ def test_mex_dropins_match_oracle(fba, oracle, mexlibs, cam0_folders, tmp_path, 
     xo, no = oracle.buildxhat(od)
     np.testing.assert_array_equal(x, xo)
     assert [r[0] for r in mx.get(names)] == no
+    if variant in MASKED:  # the partial layouts: 4 of 6 EOPs and xp, c, p1, p2 / all six EOPs and xp, yp, c
+        assert oracle.counts(od.settings) == {"mix_a_noic_pinhole": (4, 4), "stage2_pinhole": (6, 3)}[variant]
     # BuildAwG at the start values and at a perturbed xhat
     rng = np.random.default_rng(3)
     for xv in (xo, xo * (1 + 1e-4 * rng.standard_normal(len(xo)))):
@@ -207,6 +215,8 @@ def test_mex_dropins_match_oracle(fba, oracle, mexlibs, cam0_folders, tmp_path, 
         else:
             np.testing.assert_allclose(G, Go, rtol=1e-14, atol=1e-14 * np.abs(Go).max())
         np.testing.assert_allclose(ds, dso, rtol=1e-14)
+        if variant in MASKED:  # the compact n x u A; the index columns of dist_scaling exactly
+            assert A.shape == Ao.shape and np.array_equal(ds[:, :2], dso[:, :2])
     # BuildRSD with the oracle's final v and xhat (main.m:569-571)
     ro = oracle.adjust(od)
     rsd = mx.get(mx.call(fns["BuildRSD"], 1, [mx.mat(ro.v.reshape(-1, 1)), data, mx.mat(ro.xhat.reshape(-1, 1))])[0])
@@ -248,10 +258,25 @@ def test_mex_whole_loop_matches_oracle_cam0(fba, oracle, mexlibs, cam0_folders):
     shipped cam0 Stage-3 (pinhole, inner constraints, tie points, 3 control points) against the dense
     oracle: same count, the deltasum history, xhat per element <= 1e-9, v, the RSD cell, RMS, sigma0^2
     <= 1e-9, diag(Cx) and the EOP/IOP correlation blocks (main.m:446-482, :602) <= 1e-7."""
+    _whole_loop_cam0(fba, oracle, mexlibs, cam0_folders["stage3_pinhole"])
+
+
+@pytest.mark.gpu
+def test_mex_whole_loop_matches_oracle_cam0_mix_a(fba, oracle, mexlibs, tmp_path):
+    """The same gateway and assertions on cam0 under the mixed mask mix_a (Omega, Zc, yp, radial off) without
+    inner constraints: the gateway's xhat, cx_diag and corr have the compressed lengths u = 490 and
+    u_img + u_cam = 4 + 4 (restatement spread on this variant <= 1.3e-11 per element, so 1e-9 holds)."""
+    folder = variant_folder(str(tmp_path), "mix_a", MASKED["mix_a_noic_pinhole"])
+    _whole_loop_cam0(fba, oracle, mexlibs, folder, u=490, mu=8)
+
+
+def _whole_loop_cam0(fba, oracle, mexlibs, folder, u=None, mu=None):
     mx, fns = mexlibs
-    od = oracle.load_folder(cam0_folders["stage3_pinhole"])
+    od = oracle.load_folder(folder)
     ro = oracle.adjust(od)
     _, xhat, count, dsum, v, rsd, st, cxd, corr = _mex_adjust(mx, fns, od)
+    if u is not None:
+        assert mx.get(xhat).shape == (u, 1) == mx.get(cxd).shape and sum(oracle.counts(od.settings)) == mu
     assert mx.get(count)[0, 0] == ro.iterations
     # the deltasum history: the gateway runs the library's loop (fba_adjust), so the Python mirror's to
     # rounding; against the oracle the first pass at 1e-9 or 20x the restatements' own spread, the bound
@@ -259,7 +284,7 @@ def test_mex_whole_loop_matches_oracle_cam0(fba, oracle, mexlibs, cam0_folders):
     # between exact restatements: inner constraints + control points; the later passes are differences of
     # nearly equal iterates)
     d = mx.get(dsum)[0]
-    lib = fba.adjust(fba.load_folder(cam0_folders["stage3_pinhole"]), covariance=False).deltasum
+    lib = fba.adjust(fba.load_folder(folder), covariance=False).deltasum
     np.testing.assert_allclose(d, lib, rtol=0, atol=1e-12 * ro.deltasum[0])
     spread = solver_spread(oracle, od, ro)
     assert abs(d[0] - ro.deltasum[0]) <= max(1e-9, 20 * spread["deltasum0"]) * ro.deltasum[0], spread["deltasum0"]
