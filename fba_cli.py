@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Command line for the reference's two entry points on the MI355X path:
 
-    python fba_cli.py main <folder> [plot]     main(folder, plot)  (main.m:10)
+    python fba_cli.py main <folder> [plot] [--reliability]     main(folder, plot)  (main.m:10);
+                                               --reliability also writes the .rel table (report.write_rel)
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
 """
 import sys

@@ -63,14 +63,23 @@ def batch_run(paths, device=0):
     return done
 
 
+def parse_main(args):
+    """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
+    anywhere after the folder"""
+    rest = [a for a in args[1:] if a != "--reliability"]
+    return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
+
+
 def cli(argv=None):
-    """python -m fba_cli main <folder> | batch <folder>...   (main(folder, plot) / BatchRun.m)"""
+    """python -m fba_cli main <folder> [plot] [--reliability] | batch <folder>...   (main(folder, plot) /
+    BatchRun.m)"""
     argv = list(sys.argv[1:] if argv is None else argv)
     if len(argv) >= 2 and argv[0] == "main":
         from .bundle import main
-        return main(argv[1], len(argv) > 2 and argv[2] not in ("0", "false"))
+        folder, plot, reliability = parse_main(argv[1:])
+        return main(folder, plot, reliability=reliability)
     if len(argv) >= 2 and argv[0] == "batch":
         done = batch_run(argv[1:])
         return 1 if any(e for _, e in done) else 0
-    print("usage: fba_cli.py main <folder> [plot] | batch <folder>...")
+    print("usage: fba_cli.py main <folder> [plot] [--reliability] | batch <folder>...")
     return 2

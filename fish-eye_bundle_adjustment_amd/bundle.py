@@ -78,11 +78,15 @@ class Adjustment:
     seconds: float
     cx_diag: np.ndarray = None   # diag of the final Cx (sigma02-scaled, distortions de-scaled)
     corr: np.ndarray = None      # (numImg, u_img+u_cam, u_img+u_cam) EOP/IOP Correlation sub-blocks
+    redundancy: np.ndarray = None  # (2 n_pts) redundancy numbers, PHO order, x y interleaved (reliability=True)
+    wstat: np.ndarray = None       # (2 n_pts) standardised residuals w = v / (sigma sqrt(r))
 
 
-def adjust(data: Dataset, device=0, verbose=False, covariance=True) -> Adjustment:
+def adjust(data: Dataset, device=0, verbose=False, covariance=True, reliability=False) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
-    covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602)."""
+    covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
+    reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
+    redundancy numbers and standardised residuals of the image measurements."""
     t0 = time.perf_counter()
     ctx = capi.Context(data.pack(), capi.make_settings(data.settings), device=device, verbose=verbose)
     try:
@@ -90,11 +94,16 @@ def adjust(data: Dataset, device=0, verbose=False, covariance=True) -> Adjustmen
         t1 = time.perf_counter()
         xhat = ctx.get_xhat()
         v, rsd, st = ctx.residuals()
-        cxd, corr = ctx.covariance(st[3]) if covariance else (None, None)
+        red = wst = None
+        if reliability:
+            cxd, corr, red, wst = ctx.reliability(st[3])
+        else:
+            cxd, corr = ctx.covariance(st[3]) if covariance else (None, None)
     finally:
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
-                      rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr)
+                      rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
+                      redundancy=red, wstat=wst)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -106,17 +115,20 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
     par = report.write_out(out, data, res, res.seconds)
     report.write_rsd(os.path.join(folder, name + ".rsd"), data, res.rsd)
     report.write_par(os.path.join(folder, name + ".par"), par)
+    if res.redundancy is not None:
+        report.write_rel(os.path.join(folder, name + ".rel"), data, res)
     return out
 
 
-def main(folder: str = "", plot: bool = False, device=0) -> int:
+def main(folder: str = "", plot: bool = False, device=0, reliability=False) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
-    produced; `plot` is accepted for signature compatibility."""
+    produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
+    table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
         data = load_folder(folder, project_dir=None if folder == project_dir else project_dir)
-        res = adjust(data, device=device)
+        res = adjust(data, device=device, reliability=reliability)
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:
         print(f"Error: {e}")

@@ -23,7 +23,7 @@ EXPORTS = (
     "fba_destroy", "fba_solve_mode", "fba_buildxhat", "fba_set_xhat", "fba_get_xhat", "fba_build_awg",
     "fba_accumulate", "fba_reduce_buffer", "fba_synchronize", "fba_solve_update", "fba_solve_update_async",
     "fba_deltasum_device", "fba_solve_finish", "fba_step", "fba_adjust",
-    "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_last_timings", "fba_set_timing", "fba_set_probe",
+    "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability", "fba_last_timings", "fba_set_timing", "fba_set_probe",
     "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
 )
 
@@ -85,6 +85,7 @@ def _load():
         "fba_residuals": ([P, P, P, P], C.c_int),
         "fba_finish_stats": ([P, P, P, D, P], C.c_int),
         "fba_covariance": ([P, D, P, P], C.c_int),
+        "fba_reliability": ([P, D, P, P, P, P], C.c_int),
         "fba_last_timings": ([P, P], C.c_int),
         "fba_set_timing": ([P, I], C.c_int),
         "fba_set_probe": ([P, I], C.c_int),
@@ -283,6 +284,23 @@ class Context:
         cr = np.zeros((max(self.packed.n_img, 1), mu, mu)) if corr else None
         check(lib.fba_covariance(self.h, float(sigma02), ptr(d), ptr(cr)))
         return d[: int(self.u)], (cr[: self.packed.n_img] if corr else None)
+
+    def reliability(self, sigma02, corr=True):
+        """fba_reliability: (cx_diag, corr, redundancy, wstat) -- covariance()'s two outputs, bit-identical, and
+        per image measurement (PHO order, x y interleaved like v) Baarda's redundancy number r = 1 - p a Cx a'
+        and the standardised residual w = v / (sigma sqrt(r)).  Consumes the factor like covariance(): call
+        one of the two."""
+        st = self.settings
+        u_img = sum(int(x) for x in (st.est_Xc, st.est_Yc, st.est_Zc, st.est_omega, st.est_phi, st.est_kappa))
+        u_cam = (int(st.est_xp) + int(st.est_yp) + int(st.est_c) + int(st.est_radial) * int(st.num_radial)
+                 + 2 * int(st.est_decent))
+        mu = u_img + u_cam
+        n = self.packed.n_pts
+        d = np.zeros(max(int(self.u), 1))
+        cr = np.zeros((max(self.packed.n_img, 1), mu, mu)) if corr else None
+        red, wst = np.zeros(max(2 * n, 1)), np.zeros(max(2 * n, 1))
+        check(lib.fba_reliability(self.h, float(sigma02), ptr(d), ptr(cr), ptr(red), ptr(wst)))
+        return d[: int(self.u)], (cr[: self.packed.n_img] if corr else None), red[: 2 * n], wst[: 2 * n]
 
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""

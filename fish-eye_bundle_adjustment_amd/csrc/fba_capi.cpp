@@ -1500,11 +1500,17 @@ int fba_build_rsd(fba_ctx* ctx, const double* v, const double* xhat, double* rsd
     return FBA_OK;
 }
 
-int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+// fba_covariance, and with rel fba_reliability: the same launches and host code for cx_diag / corr, then the
+// reliability kernels on the same selected inverse (redundancy / wstat [2 n_pts], either may be NULL)
+static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_diag, double* corr, bool rel,
+                           double* redundancy, double* wstat) {
     if (!c) { set_error("NULL context"); return FBA_ERR_ARG; }
+    if (rel && c->sched.split) {
+        set_error("fba_reliability: not implemented for the subtree split (fba_solve_mode 1); use the replicated solve");
+        return FBA_ERR_UNSUPPORTED;
+    }
     if (!c->have_factor || !c->have_delta) {
-        set_error("fba_covariance needs the factor of the last solve (call it once, right after the iterations)");
+        set_error(std::string(who) + " needs the factor of the last solve (call it once, right after the iterations)");
         return FBA_ERR_ARG;
     }
     const Layout& L = c->L;
@@ -1536,9 +1542,23 @@ int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr) 
         set_error("hipMemsetAsync failed");
         return FBA_ERR_HIP;
     }
-    if ((rc = launch_covariance(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0))) {
+    double *d_q = nullptr, *d_red = nullptr, *d_wst = nullptr;
+    if (rel && ((rc = ws_get(*c, 69, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_obs, 1), (void**)&d_q)) ||
+                (rc = ws_get(*c, 70, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_red)) ||
+                (rc = ws_get(*c, 71, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_wst))))
+        return rc;
+    if ((rc = rel ? launch_reliability(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst)
+                  : launch_covariance(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0))) {
         release();
         return rc;
+    }
+    if (rel && c->n_pts > 0) {
+        const size_t nb = sizeof(double) * 2 * (size_t)c->n_pts;
+        if ((redundancy && hipMemcpy(redundancy, d_red, nb, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (wstat && hipMemcpy(wstat, d_wst, nb, hipMemcpyDeviceToHost) != hipSuccess)) {
+            set_error("HIP error copying the reliability back");
+            return FBA_ERR_HIP;
+        }
     }
     std::vector<double> cd(L.u_c), pd(3 * (size_t)L.n_tie), ib(corr ? (size_t)L.n_img_ref * m * m : 0);
     const hipError_t e1 = hipMemcpy(cd.data(), d_cdiag, sizeof(double) * cd.size(), hipMemcpyDeviceToHost);
@@ -1589,6 +1609,14 @@ int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr) 
         }
     }
     return FBA_OK;
+}
+
+int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr) {
+    return covariance_impl(reinterpret_cast<Ctx*>(ctx), "fba_covariance", sigma02, cx_diag, corr, false, nullptr, nullptr);
+}
+
+int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr, double* redundancy, double* wstat) {
+    return covariance_impl(reinterpret_cast<Ctx*>(ctx), "fba_reliability", sigma02, cx_diag, corr, true, redundancy, wstat);
 }
 
 int fba_finish_stats(const fba_problem* p, const fba_settings* s, const double* sums, double vtpv, double* stats) {

@@ -385,8 +385,9 @@ static bool s_split(const Ctx& c) { return c.sched.split; }
 // column j the solutions of j's ancestors -- so the selected inverse runs on the whole block pattern as
 // it stands: the other ranks' columns, never factored here, come out as garbage no output reads
 // (fba_covariance keeps the entries of this rank's rows only)
-int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
-                      const int32_t* d_icam, int n_iblk) {
+// launch_selinv: the last linearisation's tables, the border columns Z / Wz and the selected inverse Q in S --
+// what fba_covariance and fba_reliability (fba_rel.hip) share; `si` carries Z, Wz and the next free workspace slot
+int launch_selinv(Ctx& c, SelInv& si) {
     const Layout& L = c.L;
     const int64_t ld = L.ld, n_pad = L.n_pad, nb = n_pad / CB;
     const Sched& s = c.sched;
@@ -400,7 +401,8 @@ int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, 
     const int nz = L.nrhs > 1 ? 14 : 0;
     double *d_Z = nullptr, *d_Wz = nullptr, *d_h = nullptr, *d_g = nullptr;
     // scratch from the context's covariance workspace (kept across calls: no allocation per call)
-    int next_slot = 0;
+    int& next_slot = si.next_slot;
+    next_slot = 0;
     auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
     auto cleanup = [&]() {};
     if (nz) {
@@ -538,7 +540,23 @@ int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, 
             k_blk_combine<<<dim3((unsigned)(ph[3] - ph[2]), COMB_SEG), 256, 0, c.stream>>>(d_combs + 3 * ph[2], d_tasks, c.d_S, ld, d_Y, d_P);
     }
     FBA_HIP(hipGetLastError());
+    si.d_Z = d_Z;
+    si.d_Wz = d_Wz;
+    si.nz = nz;
+    si.d_T = nullptr;
+    return FBA_OK;
+}
 
+// the outputs of fba_covariance from the selected inverse (no synchronisation; S stays as launch_selinv left it)
+static int launch_cov_outputs(Ctx& c, SelInv& si, double* d_cdiag, double* d_pdiag, double* d_iblk,
+                              const int32_t* d_islot, const int32_t* d_icam, int n_iblk) {
+    const Layout& L = c.L;
+    const int64_t ld = L.ld, n_pad = L.n_pad;
+    const double *d_Z = si.d_Z, *d_Wz = si.d_Wz;
+    const int nz = si.nz;
+    int rc;
+    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, si.next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
+    auto cleanup = [&]() {};
     if (d_cdiag)
         k_cov_cam<<<(unsigned)((L.u_c + 255) / 256), 256, 0, c.stream>>>(c.d_S, ld, d_Z, d_Wz, nz, n_pad, L.u_c, L.n_img,
                                                                          L.cw, L.nk, c.d_cam_tab, c.cam_tab_stride, d_cdiag);
@@ -557,8 +575,30 @@ int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, 
                                                                       c.d_img, c.n_lp, L.n_img, L.cw, L.u_c, d_pdiag);
     FBA_HIP(hipGetLastError());
     if (d_pdiag && (rc = launch_gen_cov(c, d_Z, d_Wz, nz, d_pdiag))) { cleanup(); return rc; }
+    si.d_T = d_T;
+    return FBA_OK;
+}
+
+int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
+                      const int32_t* d_icam, int n_iblk) {
+    SelInv si;
+    int rc;
+    if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)))
+        return rc;
     FBA_HIP(hipStreamSynchronize(c.stream));
-    cleanup();
+    c.have_factor = false;
+    return FBA_OK;
+}
+
+// fba_reliability: fba_covariance's launches, then the reliability kernels on the same selected inverse
+int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
+                       const int32_t* d_icam, int n_iblk, double* d_q, double* d_red, double* d_wst) {
+    SelInv si;
+    int rc;
+    if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)) ||
+        (rc = launch_rel_outputs(c, si, d_q, d_red, d_wst)))
+        return rc;
+    FBA_HIP(hipStreamSynchronize(c.stream));
     c.have_factor = false;
     return FBA_OK;
 }

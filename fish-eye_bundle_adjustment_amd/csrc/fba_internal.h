@@ -404,6 +404,16 @@ int launch_residuals(Ctx& c);    // v per obs, partial sums
 int launch_build_rsd(Ctx& c, const double* d_v, const double* d_xpyp, double* d_rsd);  // BuildRSD for a given v
 int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
                       const int32_t* d_icam, int n_iblk);  // post-fit covariance (fba_cov.hip)
+// what the selected inverse leaves for the kernels reading it (fba_cov.hip launch_selinv): the border's Z and
+// Wz ([14][n_pad], nullptr with nz = 0), the per-observation T table once built, the next free workspace slot
+struct SelInv {
+    double *d_Z = nullptr, *d_Wz = nullptr, *d_T = nullptr;
+    int nz = 0, next_slot = 0;
+};
+int launch_selinv(Ctx& c, SelInv& si);
+int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst);  // fba_rel.hip
+int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
+                       const int32_t* d_icam, int n_iblk, double* d_q, double* d_red, double* d_wst);
 int launch_dense_awg(Ctx& c, double* dA, double* dG, const int64_t* d_map, int64_t n_rows, int64_t u_ref);
 int border_solve_selftest(int device, const double* gram, double* coef);  // fba_test_border_solve
 

@@ -19,6 +19,9 @@ LINE = "*" * 109  # main.m:635
 DECIMALS = 5      # main.m:686
 PADDING = 4       # main.m:634
 VERSION = "fba_amd 1 (MI355X HIP path)"
+MDB_DELTA0 = 4.13   # Baarda's non-centrality parameter for alpha0 = 0.1 %, beta0 = 80 % (write_rel's mdb)
+W_CRITICAL = 3.29   # two-sided 0.1 % point of the standard normal distribution (write_rel's flag)
+R_MIN = 1e-10       # below it an observation cannot be checked (fba_reliability reports w = 0)
 PRODUCER = "fba_amd, the MI355X-native HIP implementation (not the MATLAB reference)"
 
 
@@ -311,3 +314,21 @@ def write_rsd(path, data, rsd):
             r = rsd[i]
             fh.write("\t".join([data.pho_target[i], data.pho_image[i], _cell(data.xy[i, 0]), _cell(data.xy[i, 1])]
                                + [_cell(v) for v in r]) + "\n")
+
+
+def write_rel(path, data, res):
+    """The reliability table <Output_Filename stem>.rel (no reference counterpart), tab-delimited in
+    write_rsd's style: targetID, imageID, r_x, r_y, w_x, w_y, mdb_x, mdb_y, flag per image point.  r and w
+    are fba_reliability's (res.redundancy, res.wstat); mdb = MDB_DELTA0 sigma / sqrt(r) is the smallest
+    gross error the w-test detects (inf where r < R_MIN); flag is * where max(|w_x|, |w_y|) > W_CRITICAL."""
+    if res.redundancy is None or res.wstat is None:
+        raise ValueError("write_rel: the adjustment carries no reliability (adjust(..., reliability=True))")
+    r = np.asarray(res.redundancy, dtype=np.float64).reshape(-1, 2)
+    w = np.asarray(res.wstat, dtype=np.float64).reshape(-1, 2)
+    sigma = (float(data.settings["Meas_std"]), float(data.settings["Meas_std_y"]))
+    with open(path, "w") as fh:
+        for i in range(data.n_pts):
+            mdb = [MDB_DELTA0 * sigma[m] / math.sqrt(r[i, m]) if r[i, m] >= R_MIN else math.inf for m in range(2)]
+            flag = "*" if max(abs(w[i, 0]), abs(w[i, 1])) > W_CRITICAL else ""
+            fh.write("\t".join([data.pho_target[i], data.pho_image[i]]
+                               + [_cell(v) for v in (r[i, 0], r[i, 1], w[i, 0], w[i, 1], mdb[0], mdb[1])] + [flag]) + "\n")

@@ -221,6 +221,23 @@ int fba_finish_stats(const fba_problem* p, const fba_settings* s, const double* 
  *           top images on rank 0), zeros for the others. */
 int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr);
 
+/* Observation reliability (no reference counterpart: main.m stops at BuildRSD's raw residuals).  Baarda's
+ * redundancy number and standardised residual (w-test) of every image measurement, from the same factor
+ * and the same state as fba_covariance:
+ *   redundancy [2*n_pts] (may be NULL): r = 1 - p (a Cx a'), p = 1 / Meas_std^2 (Meas_std_y^2 for y), a the
+ *           observation's row of the last linearisation and Cx the cofactor matrix (main.m:428-444, before
+ *           the distortion de-scaling and the sigma02 factor); PHO order, x y interleaved like v.  The
+ *           values lie in (0, 1) and sum to n - u (+ 7 with inner constraints).
+ *   wstat [2*n_pts] (may be NULL): w = v / (sigma sqrt(r)) with fba_residuals' v; 0 where r < 1e-10 (the
+ *           observation cannot be checked).
+ * cx_diag and corr (either may be NULL) are filled exactly as by fba_covariance (bit-identical), so a
+ * caller who wants both calls this function alone: like fba_covariance it needs the factor of the last
+ * solve and consumes it (FBA_ERR_ARG otherwise).  With world > 1 and the replicated solve a rank fills its
+ * own observations and writes 0 elsewhere (the ranks' outputs sum to the whole vectors).  With the subtree
+ * split (fba_solve_mode gives 1) it returns FBA_ERR_UNSUPPORTED and leaves the factor in place. */
+int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr,
+                    double* redundancy /*[2*n_pts]*/, double* wstat /*[2*n_pts]*/);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
