@@ -4,6 +4,9 @@
     python fba_cli.py main <folder> [plot] [--reliability]     main(folder, plot)  (main.m:10);
                                                --reliability also writes the .rel table (report.write_rel)
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
+    ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
+                                               of sigma (default: the 95 %-efficiency constants, huber 1.345,
+                                               cauchy 2.385); also writes the .wgt table (report.write_wgt)
 """
 import sys
 

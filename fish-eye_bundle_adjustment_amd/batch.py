@@ -47,39 +47,86 @@ def find_folders(folder, exts=EXTS, log=print):
     return out
 
 
-def batch_run(paths, device=0):
+def batch_run(paths, device=0, robust=None, robust_k=None):
     """BatchRun.m:42-66: every data folder under the selected paths through main(folder, false);
-    stops at the first folder whose main() fails.  Returns the list of (folder, main_error)."""
+    stops at the first folder whose main() fails.  Returns the list of (folder, main_error).
+    robust / robust_k: the robust loss of bundle.adjust, for every folder."""
     from .bundle import main
     folders = []
     for p in paths:
         folders.extend(find_folders(p))
     done = []
     for f in folders:
-        err = main(f, False, device=device)
+        err = main(f, False, device=device, **_robust_kw(robust, robust_k))
         done.append((f, err))
         if err == 1:
             break
     return done
 
 
+def _robust_kw(robust, robust_k):
+    """main()'s keywords for a robust loss; none without one, so the call is the one it was"""
+    return {"robust": robust, "robust_k": robust_k} if robust else {}
+
+
+def parse_robust(args):
+    """--robust huber[:k] | cauchy[:k] (also --robust=...) anywhere in args -> (args without it, loss or None,
+    k or None).  ValueError for a missing or unknown loss, or a k that is not a positive number."""
+    rest, spec = [], None
+    it = iter(args)
+    for a in it:
+        if a == "--robust":
+            spec = next(it, None)
+            if spec is None:
+                raise ValueError("--robust needs huber[:k] or cauchy[:k]")
+        elif a.startswith("--robust="):
+            spec = a.split("=", 1)[1]
+        else:
+            rest.append(a)
+    if spec is None:
+        return rest, None, None
+    loss, _, ks = spec.partition(":")
+    loss = loss.lower()
+    if loss not in ("huber", "cauchy"):
+        raise ValueError(f"--robust: unknown loss {loss!r} (huber or cauchy)")
+    k = None
+    if ks:
+        k = float(ks)
+        if not (k > 0.0 and k < float("inf")):
+            raise ValueError("--robust: k must be a positive number")
+    return rest, loss, k
+
+
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
-    anywhere after the folder"""
+    anywhere after the folder (a --robust option is parse_robust's)"""
+    args = parse_robust(args)[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--robust LOSS[:k]] | batch <folder>... "
+         "[--robust LOSS[:k]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, re-weighted at "
+         "every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber 1.345, cauchy "
+         "2.385; writes the .wgt table")
+
+
 def cli(argv=None):
-    """python -m fba_cli main <folder> [plot] [--reliability] | batch <folder>...   (main(folder, plot) /
-    BatchRun.m)"""
+    """python -m fba_cli main <folder> [plot] [--reliability] [--robust LOSS[:k]] | batch <folder>...
+    [--robust LOSS[:k]]   (main(folder, plot) / BatchRun.m); LOSS huber (k = 1.345) or cauchy (k = 2.385)"""
     argv = list(sys.argv[1:] if argv is None else argv)
+    try:
+        argv, robust, robust_k = parse_robust(argv)
+    except ValueError as e:
+        print(f"Error: {e}")
+        print(USAGE)
+        return 2
     if len(argv) >= 2 and argv[0] == "main":
         from .bundle import main
         folder, plot, reliability = parse_main(argv[1:])
-        return main(folder, plot, reliability=reliability)
+        return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k))
     if len(argv) >= 2 and argv[0] == "batch":
-        done = batch_run(argv[1:])
+        done = batch_run(argv[1:], **_robust_kw(robust, robust_k))
         return 1 if any(e for _, e in done) else 0
-    print("usage: fba_cli.py main <folder> [plot] [--reliability] | batch <folder>...")
+    print(USAGE)
     return 2

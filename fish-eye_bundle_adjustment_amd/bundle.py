@@ -80,20 +80,40 @@ class Adjustment:
     corr: np.ndarray = None      # (numImg, u_img+u_cam, u_img+u_cam) EOP/IOP Correlation sub-blocks
     redundancy: np.ndarray = None  # (2 n_pts) redundancy numbers, PHO order, x y interleaved (reliability=True)
     wstat: np.ndarray = None       # (2 n_pts) standardised residuals w = v / (sigma sqrt(r))
+    weights: np.ndarray = None     # (2 n_pts) effective weights, user weight x loss factor (weights= / robust=)
 
 
-def adjust(data: Dataset, device=0, verbose=False, covariance=True, reliability=False) -> Adjustment:
+def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
+           reliability=False) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
-    redundancy numbers and standardised residuals of the image measurements."""
+    redundancy numbers and standardised residuals of the image measurements.
+
+    No reference counterpart: weights ((2 n_pts), PHO order, x y interleaved) multiply the a-priori weights
+    (fba_set_weights); robust ("huber" / "cauchy", robust_k in units of sigma, default capi.LOSS_K) first
+    iterates with L2 to the reference's stopping rule -- at the starting values every misclosure is large and a
+    loss would down-weight everything -- then sets the loss and continues under the same threshold and the
+    remaining Iteration_Cap.  Residuals, sigma0^2, covariance and reliability are those of the final,
+    re-weighted state; Adjustment.weights holds the effective weights."""
     t0 = time.perf_counter()
     ctx = capi.Context(data.pack(), capi.make_settings(data.settings), device=device, verbose=verbose)
     try:
+        if weights is not None:
+            ctx.set_weights(weights)
         it, hist = ctx.adjust()
+        if robust:
+            ctx.set_loss(robust, robust_k)
+            cap, thr = max(int(ctx.settings.iteration_cap), 1), float(ctx.settings.threshold)
+            more, deltasum = [], 100.0  # main.m:407, :412, :490-493 again, on what the L2 loop left of the cap
+            while deltasum > thr and it + len(more) < cap:
+                deltasum = ctx.step()
+                more.append(deltasum)
+            it, hist = it + len(more), np.concatenate([hist, more])
         t1 = time.perf_counter()
         xhat = ctx.get_xhat()
         v, rsd, st = ctx.residuals()
+        eff = ctx.get_weights() if (weights is not None or robust) else None
         red = wst = None
         if reliability:
             cxd, corr, red, wst = ctx.reliability(st[3])
@@ -103,7 +123,7 @@ def adjust(data: Dataset, device=0, verbose=False, covariance=True, reliability=
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst)
+                      redundancy=red, wstat=wst, weights=eff)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -117,18 +137,21 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
     report.write_par(os.path.join(folder, name + ".par"), par)
     if res.redundancy is not None:
         report.write_rel(os.path.join(folder, name + ".rel"), data, res)
+    if res.weights is not None:
+        report.write_wgt(os.path.join(folder, name + ".wgt"), data, res)
     return out
 
 
-def main(folder: str = "", plot: bool = False, device=0, reliability=False) -> int:
+def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
-    table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it."""
+    table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
+    adjust()'s robust loss; the .wgt table (report.write_wgt) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
         data = load_folder(folder, project_dir=None if folder == project_dir else project_dir)
-        res = adjust(data, device=device, reliability=reliability)
+        res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k)
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:
         print(f"Error: {e}")

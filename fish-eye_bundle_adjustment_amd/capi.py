@@ -15,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfba.so")
 
 TYPES = ("fisheye", "pinhole", "equisolid", "orthographic", "stereographic")
+LOSSES = ("none", "huber", "cauchy")  # FBA_LOSS_*
+# the usual 95 %-efficiency tuning constants (in units of sigma)
+LOSS_K = {"huber": 1.345, "cauchy": 2.385}
 NK_MAX = 8
 
 # every symbol include/fba.h declares
@@ -23,7 +26,8 @@ EXPORTS = (
     "fba_destroy", "fba_solve_mode", "fba_buildxhat", "fba_set_xhat", "fba_get_xhat", "fba_build_awg",
     "fba_accumulate", "fba_reduce_buffer", "fba_synchronize", "fba_solve_update", "fba_solve_update_async",
     "fba_deltasum_device", "fba_solve_finish", "fba_step", "fba_adjust",
-    "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability", "fba_last_timings", "fba_set_timing", "fba_set_probe",
+    "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability",
+    "fba_set_weights", "fba_set_loss", "fba_get_weights", "fba_last_timings", "fba_set_timing", "fba_set_probe",
     "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
 )
 
@@ -86,6 +90,9 @@ def _load():
         "fba_finish_stats": ([P, P, P, D, P], C.c_int),
         "fba_covariance": ([P, D, P, P], C.c_int),
         "fba_reliability": ([P, D, P, P, P, P], C.c_int),
+        "fba_set_weights": ([P, P], C.c_int),
+        "fba_set_loss": ([P, I, D], C.c_int),
+        "fba_get_weights": ([P, P], C.c_int),
         "fba_last_timings": ([P, P], C.c_int),
         "fba_set_timing": ([P, I], C.c_int),
         "fba_set_probe": ([P, I], C.c_int),
@@ -301,6 +308,35 @@ class Context:
         red, wst = np.zeros(max(2 * n, 1)), np.zeros(max(2 * n, 1))
         check(lib.fba_reliability(self.h, float(sigma02), ptr(d), ptr(cr), ptr(red), ptr(wst)))
         return d[: int(self.u)], (cr[: self.packed.n_img] if corr else None), red[: 2 * n], wst[: 2 * n]
+
+    def set_weights(self, weights=None):
+        """fba_set_weights: per-measurement multipliers of the a-priori weight, (2 n_pts) in PHO order, x y
+        interleaved like v (or (n_pts, 2)); None restores all 1.  Entries must be finite and > 0."""
+        if weights is None:
+            check(lib.fba_set_weights(self.h, None))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != 2 * self.packed.n_pts:
+            raise ValueError("set_weights: weights must have 2*n_pts entries")
+        check(lib.fba_set_weights(self.h, ptr(w)))
+
+    def set_loss(self, loss="none", k=None):
+        """fba_set_loss: "none", "huber" or "cauchy" (or the FBA_LOSS_* number); k in units of sigma, by
+        default the 95 %-efficiency constant of the loss (LOSS_K)."""
+        if isinstance(loss, str):
+            if loss.lower() not in LOSSES:
+                raise ValueError(f"set_loss: unknown loss {loss!r} (one of {', '.join(LOSSES)})")
+            loss = LOSSES.index(loss.lower())
+        if k is None:
+            k = LOSS_K.get(LOSSES[loss], 0.0) if 0 <= int(loss) < len(LOSSES) else 0.0
+        check(lib.fba_set_loss(self.h, int(loss), float(k)))
+
+    def get_weights(self):
+        """fba_get_weights: the effective weights (user weight x loss factor) at the last linearisation point,
+        (2 n_pts) in PHO order; other ranks' observations are 0."""
+        w = np.zeros(max(2 * self.packed.n_pts, 1))
+        check(lib.fba_get_weights(self.h, ptr(w)))
+        return w[: 2 * self.packed.n_pts]
 
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""

@@ -168,7 +168,7 @@ static void destroy(Ctx* c) {
                     c->d_acc, c->d_ppart, c->d_U, c->d_ipart, c->d_cpart, c->d_cseg, c->d_bscr, c->d_gblk, c->d_lrprof, c->d_ptrace, c->d_gpairs, c->d_red, c->d_xfull, c->d_xlin, c->d_delta, c->d_img_tab, c->d_cam_tab, c->d_G, c->d_J, c->d_WT,
                     c->d_pt_tab, c->d_P, c->d_flags, c->d_S, c->d_X, c->d_dinv, c->d_linv, c->d_scal, c->d_part, c->d_res, c->d_caminfo,
                     c->d_active, c->d_counted, c->d_obs_pho, c->d_sched, c->d_gpt, c->d_gcu, c->d_gug, c->d_xpart,
-                    c->d_kpart, c->d_bown, c->d_rown, c->d_topdiag};
+                    c->d_kpart, c->d_bown, c->d_rown, c->d_topdiag, c->d_sw, c->d_seff, c->d_weff};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (auto& w : c->ws)
@@ -1298,7 +1298,9 @@ int fba_build_awg(fba_ctx* ctx, const double* xhat, double* A, double* w, double
     if (!c) { set_error("NULL context"); return FBA_ERR_ARG; }
     int rc;
     if (xhat && (rc = set_xhat_ref(c, xhat))) return rc;
-    if ((rc = launch_params(*c)) || (rc = launch_linearize(*c))) return rc;
+    // the reference's raw A, w whatever weights / loss are set; every reader of d_J linearises again first
+    // (fba_residuals, fba_covariance), and have_lin is cleared below, so the raw rows are never read as whitened
+    if ((rc = launch_params(*c)) || (rc = launch_linearize(*c, nullptr, true))) return rc;
     const Layout& L = c->L;
     const int64_t n = 2 * c->n_pts, u = L.u_ref;
     double *dA = nullptr, *dW = nullptr;
@@ -1471,6 +1473,106 @@ int fba_residuals(fba_ctx* ctx, double* v, double* rsd, double* stats) {
         stats[4] = sp;
         stats[5] = nu;
     }
+    return FBA_OK;
+}
+
+// ---- per-observation weights and robust loss (no reference counterpart) ----
+namespace fba {
+// the three [2 n_obs] buffers, on first use
+static int weight_buffers(Ctx* c) {
+    if (c->d_sw) return FBA_OK;
+    const size_t n = 2 * (size_t)std::max<int64_t>(c->n_obs, 1);
+    int rc;
+    if ((rc = dalloc(&c->d_sw, n)) || (rc = dalloc(&c->d_seff, n)) || (rc = dalloc(&c->d_weff, n))) return rc;
+    return FBA_OK;
+}
+// a change of the weighting: the captured accumulation holds the old kernel arguments, and neither the
+// linearisation nor the factor of the last solve belongs to the new weights
+static int weighting_changed(Ctx* c) {
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    if (c->graph[0]) {
+        (void)hipGraphExecDestroy(c->graph[0]);
+        c->graph[0] = nullptr;
+    }
+    c->have_lin = false;
+    c->have_factor = false;
+    return FBA_OK;
+}
+}  // namespace fba
+
+int fba_set_weights(fba_ctx* ctx, const double* weight) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_set_weights: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_set_weights between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const int64_t n = 2 * c->n_pts;
+    bool all_one = true;  // all 1 is NULL: the unweighted kernels, whose arithmetic the weighted ones match
+                          // only to rounding (s = 1 is exact, the compiler's contraction around it is not the same)
+    if (weight)
+        for (int64_t i = 0; i < n; ++i) {
+            all_one = all_one && weight[i] == 1.0;
+            if (!std::isfinite(weight[i]) || !(weight[i] > 0.0)) {
+                char buf[160];
+                snprintf(buf, sizeof buf, "fba_set_weights: weight[%ld] = %g (PHO row %ld, %c) must be finite and > 0",
+                         (long)i, weight[i], (long)(i / 2), i % 2 ? 'y' : 'x');
+                set_error(buf);
+                return FBA_ERR_ARG;
+            }
+        }
+    int rc;
+    if ((rc = weighting_changed(c))) return rc;
+    if (!weight || all_one) {
+        c->weights_on = false;
+        return FBA_OK;
+    }
+    if ((rc = weight_buffers(c))) return rc;
+    double* d_w = nullptr;
+    if ((rc = ws_get(*c, 72, sizeof(double) * (size_t)std::max<int64_t>(n, 1), (void**)&d_w))) return rc;
+    if (n > 0) FBA_HIP(hipMemcpyAsync(d_w, weight, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_set_weights(*c, d_w))) return rc;
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    c->weights_on = true;
+    return FBA_OK;
+}
+
+int fba_set_loss(fba_ctx* ctx, int32_t loss, double k) {
+    if (loss != FBA_LOSS_NONE && loss != FBA_LOSS_HUBER && loss != FBA_LOSS_CAUCHY) {
+        set_error("fba_set_loss: unknown loss (FBA_LOSS_NONE, FBA_LOSS_HUBER or FBA_LOSS_CAUCHY)");
+        return FBA_ERR_ARG;
+    }
+    if (loss != FBA_LOSS_NONE && (!std::isfinite(k) || !(k > 0.0))) {
+        set_error("fba_set_loss: k (in units of sigma) must be finite and > 0");
+        return FBA_ERR_ARG;
+    }
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_set_loss: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_set_loss between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    int rc;
+    if ((rc = weighting_changed(c)) || (loss != FBA_LOSS_NONE && (rc = weight_buffers(c)))) return rc;
+    c->loss = loss;
+    c->loss_k = loss == FBA_LOSS_NONE ? 0.0 : k;
+    return FBA_OK;
+}
+
+int fba_get_weights(fba_ctx* ctx, double* weight) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !weight) { set_error("fba_get_weights: NULL argument"); return FBA_ERR_ARG; }
+    if (!c->have_lin || !c->have_delta) { set_error("fba_get_weights needs at least one iteration"); return FBA_ERR_ARG; }
+    const int64_t n = 2 * c->n_pts;
+    if (!c->whiten_on()) {  // neither weights nor a loss (the kernels write none): 1 for this rank's observations
+        std::fill(weight, weight + n, 0.0);
+        for (int64_t o = 0; o < c->n_obs; ++o) weight[2 * c->obs_pho[o]] = weight[2 * c->obs_pho[o] + 1] = 1.0;
+        return FBA_OK;
+    }
+    // the weights of the last linearisation: its rows again, as fba_residuals (k_residuals writes s^2)
+    int rc;
+    if ((rc = launch_params(*c, c->d_xlin)) || (rc = launch_linearize(*c, c->d_xlin)) || (rc = launch_residuals(*c)))
+        return rc;
+    double* d_w = nullptr;
+    if ((rc = ws_get(*c, 72, sizeof(double) * (size_t)std::max<int64_t>(n, 1), (void**)&d_w))) return rc;
+    if (n > 0) FBA_HIP(hipMemsetAsync(d_w, 0, sizeof(double) * n, c->stream));
+    if ((rc = launch_get_weights(*c, d_w))) return rc;
+    if (n > 0) FBA_HIP(hipMemcpyAsync(weight, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    FBA_HIP(hipStreamSynchronize(c->stream));
     return FBA_OK;
 }
 

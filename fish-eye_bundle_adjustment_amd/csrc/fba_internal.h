@@ -193,6 +193,15 @@ struct GenPlan {
     int64_t pk_slot = 0, ik_slot = 0;   // AccPlan::pk_slot / ik_slot (the keys' rows in ppart / ipart)
 };
 
+// Per-observation whitening of the linearising kernels (whiten_rows, fba_kernels.hip): sw holds
+// sqrt(user weight) per observation row in local order ([2 n_obs], x y interleaved; nullptr: all 1),
+// loss / k the robust loss (FBA_LOSS_*, k in units of sigma).  Both off: the kernels skip the helper.
+struct Whiten {
+    const double* sw = nullptr;
+    int loss = 0;
+    double k = 0.0;
+};
+
 struct Ctx {
     fba_problem prob{};   // shallow copy (pointers valid only during fba_create)
     fba_settings set{};
@@ -321,6 +330,15 @@ struct Ctx {
     uint8_t* d_active = nullptr; // [n_pad] 1 = estimated camera-side parameter
     uint8_t* d_counted = nullptr;// [u_full] 1 = counted in this rank's sumabs share
     int64_t* d_obs_pho = nullptr;// [n_obs] PHO row of each local observation
+    // per-observation weights and robust loss (fba_set_weights / fba_set_loss; allocated on first use)
+    double* d_sw = nullptr;      // [2*n_obs] sqrt(user weight), local order
+    double* d_seff = nullptr;    // [2*n_obs] s = sqrt(weight x loss factor) of the last k_lin_point run
+    double* d_weff = nullptr;    // [2*n_obs] effective weights s^2 (k_residuals, for fba_get_weights)
+    bool weights_on = false;     // d_sw holds user weights
+    int loss = 0;                // FBA_LOSS_*
+    double loss_k = 0.0;
+    bool whiten_on() const { return weights_on || loss != 0; }
+    Whiten whiten() const { return Whiten{weights_on ? d_sw : nullptr, loss, loss_k}; }
     double* h_pinned = nullptr;  // pinned host scratch (coherent, mapped: k_sum_parts writes scal[0..3] here,
                                  // then [4] = its running count of solves, scal[5])
     double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[4])
@@ -380,8 +398,9 @@ std::vector<int32_t> camera_order(const fba_problem* p);  // internal image slot
 void build_schedule(Ctx& c, const std::vector<std::pair<int32_t, int32_t>>& pairs);  // pairs: (e1, e2) slots, e1 > e2
 int launch_params(Ctx& c, const double* x = nullptr, double* copy_to = nullptr);  // x: parameters (default d_xfull),
                                                                                    // also copied to copy_to
-int launch_linearize(Ctx& c, const double* x = nullptr);  // Jacobian rows to d_J (residuals, dense AwG)
-int launch_linearize_range(Ctx& c, const double* x, int64_t c0, int64_t c1);  // chunks [c0, c1) only
+// raw: no whitening (fba_build_awg's A, w)
+int launch_linearize(Ctx& c, const double* x = nullptr, bool raw = false);  // Jacobian rows to d_J (residuals, dense AwG)
+int launch_linearize_range(Ctx& c, const double* x, int64_t c0, int64_t c1, bool raw = false);  // chunks [c0, c1) only
 // general tie points (fba_general.hip): Jacobian rows of their observations + point tables
 // (gen_tables), their partials (gen_keys), the blocks only they touch (gen_reduce, after
 // launch_accumulate), back-substitution (gen_backsub), tie variances (gen_cov, fba_cov.hip)
@@ -401,6 +420,8 @@ int launch_pack_split(Ctx& c, int dir);      // subtree split's reduce buffer: 0
 int launch_backward(Ctx& c);     // border combine + backward solve -> delta_c
 int launch_backsub_update(Ctx& c);
 int launch_residuals(Ctx& c);    // v per obs, partial sums
+int launch_set_weights(Ctx& c, const double* d_wpho);   // d_sw[local] = sqrt(d_wpho[PHO])
+int launch_get_weights(Ctx& c, double* d_wpho);         // d_wpho[PHO] = d_weff[local] (own rows only)
 int launch_build_rsd(Ctx& c, const double* d_v, const double* d_xpyp, double* d_rsd);  // BuildRSD for a given v
 int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
                       const int32_t* d_icam, int n_iblk);  // post-fit covariance (fba_cov.hip)

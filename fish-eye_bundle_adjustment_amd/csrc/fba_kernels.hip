@@ -298,20 +298,53 @@ __device__ __forceinline__ void obs_model(double x, double y, const double* __re
     w1 = fy - y;
 }
 
+// Whitening of one image point (no reference counterpart: main.m:397-402 weights every observation alike):
+// s = sqrt(user weight x loss factor) per row, applied to the two Jacobian rows and the misclosure, so that
+// everything formed from them with the scalar px / py -- N, u, the Schur terms, the records, T, the selected
+// inverse, q -- carries P = diag(s^2 px, s^2 py).  The loss factor is a function of the point's standardised
+// misclosure t^2 = px (s0 w0)^2 + py (s1 w1)^2 with the user weights in (IRLS: evaluated at every
+// linearisation), the same for both rows: Huber 1 (t <= k) | k / t, Cauchy 1 / (1 + t^2 / k^2); both
+// continuous in t.  Only the WH = true instantiations of the linearising kernels call it; the WH = false ones,
+// launched when neither weights nor a loss are set, are the kernels as they were (a run-time branch around the
+// call changed which multiplies and adds the compiler contracts downstream: xhat moved by 1e-11 relative).
+template <int NJ>
+__device__ __forceinline__ void whiten_rows(const Whiten& wh, int64_t o, double px, double py, double (&jr)[2][NJ],
+                                            double& w0, double& w1, double& s0, double& s1) {
+    s0 = 1.0;
+    s1 = 1.0;
+    if (wh.sw) {
+        const double2 sv = *reinterpret_cast<const double2*>(wh.sw + 2 * o);
+        s0 = sv.x;
+        s1 = sv.y;
+    }
+    if (wh.loss) {
+        const double a = s0 * w0, b = s1 * w1;
+        const double t2 = px * a * a + py * b * b, k2 = wh.k * wh.k;
+        const double f = wh.loss == FBA_LOSS_HUBER ? (t2 <= k2 ? 1.0 : wh.k / sqrt(t2)) : 1.0 / (1.0 + t2 / k2);
+        const double sf = sqrt(f);
+        s0 *= sf;
+        s1 *= sf;
+    }
+#pragma unroll
+    for (int q = 0; q < NJ; ++q) { jr[0][q] *= s0; jr[1][q] *= s1; }
+    w0 *= s0;
+    w1 *= s1;
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_lin_point: one workgroup per chunk of whole tie points (<= 256 observations), one thread per
 // image point.  (1) linearise and store J; (2) one thread per point reduces its observations
 // (staged in LDS): V = Jp'PJp, b = Jp'Pw, Wc = Jc'PJp, Vinv, vb, Tc; (3) one thread per observation
 // stores its record (OBS_REC).  Chunks of control observations run step (1) only.
 // ------------------------------------------------------------------------------------------------
-template <int NK>
+template <int NK, bool WH>
 __global__ __launch_bounds__(256) void k_lin_point(
     const double* __restrict__ xy, const int32_t* __restrict__ img, const int32_t* __restrict__ cam,
     const int32_t* __restrict__ pt, const int32_t* __restrict__ lp_tie, const double* __restrict__ ctl,
     const double* __restrict__ xfull, const double* __restrict__ img_tab, const double* __restrict__ cam_tab,
     const int32_t* __restrict__ chunk_obs, const int32_t* __restrict__ chunk_pt, const int32_t* __restrict__ lp_start,
     double* __restrict__ J, double* __restrict__ WT, double* __restrict__ PT, int64_t u_c, int type, int cam_stride,
-    unsigned eop_mask, unsigned cam_mask, double px, double py, int c_off) {
+    unsigned eop_mask, unsigned cam_mask, double px, double py, int c_off, const Whiten wh, double* __restrict__ seff) {
     using LY = Lay<NK>;
     constexpr int CW = LY::CW, NJ = LY::NJ, JS = LY::JS, PS = LY::PS;
     constexpr int SH = 8 + 2 * CW;  // Jp (2x3), w (2), Jc (2xCW)
@@ -340,6 +373,11 @@ __global__ __launch_bounds__(256) void k_lin_point(
         }
         obs_model<NK>(x, y, img_tab + (int64_t)e * IMG_TAB, cam_tab + (int64_t)k * cam_stride, X, Y, Z, p >= 0, type,
                       eop_mask, cam_mask, jr, w0, w1);
+        if constexpr (WH) {  // J, the tables and the records hold whitened rows; s for k_residuals
+            double s0, s1;
+            whiten_rows<NJ>(wh, o, px, py, jr, w0, w1, s0, s1);
+            *reinterpret_cast<double2*>(seff + 2 * (int64_t)o) = double2{s0, s1};
+        }
         double* Jo = J + (int64_t)o * JS;
 #pragma unroll
         for (int q = 0; q < NJ; q += 1) { Jo[q] = jr[0][q]; Jo[NJ + q] = jr[1][q]; }
@@ -466,7 +504,7 @@ struct LR {
 
 constexpr int LR_THREADS = 512;  // observation phases use the first CHUNK_OBS threads, (D) all of them
 
-template <int NK, int IKL>
+template <int NK, int IKL, bool WH>
 __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     const double* __restrict__ xy, const int32_t* __restrict__ img, const int32_t* __restrict__ cam,
     const int32_t* __restrict__ pt, const int32_t* __restrict__ lp_tie, const double* __restrict__ ctl,
@@ -476,7 +514,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     double* __restrict__ ppart, double* __restrict__ ipart, double* __restrict__ cpart, int64_t u_c, int type,
     int cam_stride, unsigned eop_mask, unsigned cam_mask, double px, double py, uint64_t* __restrict__ tprof,
     int n_chunks, double* __restrict__ S, int64_t ld, const int32_t* __restrict__ zblk,
-    const int32_t* __restrict__ xoff, double* __restrict__ Ug) {
+    const int32_t* __restrict__ xoff, double* __restrict__ Ug, const Whiten wh) {
     using LY = Lay<NK>;
     using R_ = LR<NK>;
     if ((int)blockIdx.x >= n_chunks) {  // tail workgroups: zero one 128x128 block of the factor's pattern
@@ -569,6 +607,10 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
         const double X = q[0], Y = q[1], Z = q[2];
         obs_model<NK>(xyv.x, xyv.y, img_tab + (int64_t)e * IMG_TAB, cam_tab + (int64_t)k * cam_stride, X, Y, Z, p >= 0,
                       type, eop_mask, cam_mask, jr, w0, w1);
+        if constexpr (WH) {  // per-observation weights / robust loss: whitened rows from here on
+            double s0, s1;
+            whiten_rows<NJ>(wh, o, px, py, jr, w0, w1, s0, s1);
+        }
         if (p >= 0) {
             double* q = QE + t * ES;  // Jp (2x3) | w (2) | Jc (2xCW), raw
 #pragma unroll
@@ -1405,14 +1447,15 @@ __global__ void k_sum_parts(const double* __restrict__ part, int n, double* __re
 // residuals: v = J delta + w (main.m:569; delta = de-scaled last correction, as the reference),
 // RSD (BuildRSD.m:29-40) with xp,yp of the updated parameters; block partials of vx^2, vy^2, v'Pv
 // ------------------------------------------------------------------------------------------------
-template <int NK>
+template <int NK, bool WH>
 __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ J, const double* __restrict__ xy,
                                                    const int32_t* __restrict__ img, const int32_t* __restrict__ cam,
                                                    const int32_t* __restrict__ pt, const int32_t* __restrict__ lp_tie,
                                                    const double* __restrict__ delta, const double* __restrict__ xfull,
                                                    double* __restrict__ v, double* __restrict__ rsd,
                                                    double* __restrict__ part, int64_t n_obs, int64_t u_c, int n_img,
-                                                   double px, double py) {
+                                                   double px, double py, const double* __restrict__ seff,
+                                                   double* __restrict__ weff) {
     using LY = Lay<NK>;
     constexpr int CW = LY::CW, NJ = LY::NJ, JS = LY::JS;
     __shared__ double red[3][256];
@@ -1439,6 +1482,17 @@ __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ J,
             }
             vv[r] = acc;
         }
+        // WH: J holds whitened rows (seff: s of k_lin_point's whiten_rows): v'Pv from the whitened v,
+        // everything reported in pixels from v / s, the effective weights s^2 for fba_get_weights
+        double spw = 0.0;
+        if constexpr (WH) {
+            const double s0 = seff[2 * o], s1 = seff[2 * o + 1];
+            spw = px * (vv[0] * vv[0]) + py * (vv[1] * vv[1]);
+            vv[0] /= s0;
+            vv[1] /= s1;
+            weff[2 * o] = s0 * s0;
+            weff[2 * o + 1] = s1 * s1;
+        }
         v[2 * o] = vv[0];
         v[2 * o + 1] = vv[1];
         const double* kp = xfull + 6 * (int64_t)n_img + (int64_t)k * CW;
@@ -1454,6 +1508,7 @@ __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ J,
         sx = vv[0] * vv[0];
         sy = vv[1] * vv[1];
         sp = px * sx + py * sy;
+        if constexpr (WH) sp = spw;
     }
     red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sy; red[2][threadIdx.x] = sp;
     __syncthreads();
@@ -1583,18 +1638,24 @@ int launch_params(Ctx& c, const double* x, double* copy_to) {
 }
 
 // Jacobian rows of every observation (+ the regular points' tables): residuals, dense AwG, covariance
-int launch_linearize(Ctx& c, const double* x) { return launch_linearize_range(c, x, 0, c.n_chunks); }
+int launch_linearize(Ctx& c, const double* x, bool raw) { return launch_linearize_range(c, x, 0, c.n_chunks, raw); }
 
-int launch_linearize_range(Ctx& c, const double* x, int64_t c0, int64_t c1) {
+int launch_linearize_range(Ctx& c, const double* x, int64_t c0, int64_t c1, bool raw) {
     if (c1 <= c0) return FBA_OK;
+    const Whiten wh = raw ? Whiten{} : c.whiten();
     const unsigned em = eop_mask(c.set), cm = cam_mask(c.set, c.L.nk);
-#define LIN(NKV)                                                                                               \
-    k_lin_point<NKV><<<(unsigned)(c1 - c0), 256, 0, c.stream>>>(                                               \
-        c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, x ? x : c.d_xfull, c.d_img_tab, c.d_cam_tab,     \
+#define LIN_ARGS                                                                                               \
+    c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, x ? x : c.d_xfull, c.d_img_tab, c.d_cam_tab,         \
         c.d_chunk_obs, c.d_chunk_pt, c.d_lp_start, c.d_J, c.d_WT, c.d_pt_tab, c.L.u_c, c.set.type,              \
-        c.cam_tab_stride, em, cm, px_of(c), py_of(c), (int)c0)
+        c.cam_tab_stride, em, cm, px_of(c), py_of(c), (int)c0, wh, c.d_seff
+#define LIN(NKV)                                                                                               \
+    if (wh.sw || wh.loss)                                                                                      \
+        k_lin_point<NKV, true><<<(unsigned)(c1 - c0), 256, 0, c.stream>>>(LIN_ARGS);                           \
+    else                                                                                                       \
+        k_lin_point<NKV, false><<<(unsigned)(c1 - c0), 256, 0, c.stream>>>(LIN_ARGS)
     FBA_NK_DISPATCH(c.L.nk, LIN);
 #undef LIN
+#undef LIN_ARGS
     FBA_HIP(hipGetLastError());
     return FBA_OK;
 }
@@ -1631,12 +1692,16 @@ int launch_accumulate(Ctx& c, bool zeroed) {
     c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, c.d_xfull, c.d_img_tab, c.d_cam_tab, c.d_chunk_obs,    \
         c.d_chunk_pt, c.d_lp_start, c.d_acc, c.acc, c.d_WT, c.d_pt_tab, c.d_ppart, c.d_ipart, c.d_cpart, c.L.u_c, \
         c.set.type, c.cam_tab_stride, em, cm, px, py, c.d_lrprof, (int)nlr, c.d_S, L.ld, c.d_sched + c.sched.zero, \
-        c.d_xoff, c.d_U
+        c.d_xoff, c.d_U, c.whiten()
 #define ACC(NKV)                                                                                                  \
-    if (nlr > 0 && c.ik_lanes == 4)                                                                               \
-        k_lin_reduce<NKV, 4><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);           \
+    if (nlr > 0 && c.ik_lanes == 4 && !c.whiten_on())                                                             \
+        k_lin_reduce<NKV, 4, false><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);    \
+    else if (nlr > 0 && !c.whiten_on())                                                                           \
+        k_lin_reduce<NKV, 8, false><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);    \
+    else if (nlr > 0 && c.ik_lanes == 4)                                                                          \
+        k_lin_reduce<NKV, 4, true><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);     \
     else if (nlr > 0)                                                                                             \
-        k_lin_reduce<NKV, 8><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);           \
+        k_lin_reduce<NKV, 8, true><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);     \
     {                                                                                                             \
         const int npb = (int)((c.n_pairs + RP_PER_WG - 1) / RP_PER_WG), nib = L.n_img, ncb = (L.n_cam * CAM_SEG + 1) / 2;   \
         k_red_blocks<NKV><<<(unsigned)(npb + nib + ncb), 256, 0, c.stream>>>(                                     \
@@ -1655,13 +1720,17 @@ int launch_accumulate(Ctx& c, bool zeroed) {
 }
 
 int acc_setup(Ctx& c) {
-#define SET(NKV)                                                                                                     \
-    FBA_HIP(hipFuncSetAttribute((const void*)k_lin_reduce<NKV, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
-                                (int)LR<NKV>::LDS));                                                                  \
-    FBA_HIP(hipFuncSetAttribute((const void*)k_lin_reduce<NKV, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
+#define SET1(NKV, IKL, WH)                                                                                           \
+    FBA_HIP(hipFuncSetAttribute((const void*)k_lin_reduce<NKV, IKL, WH>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)LR<NKV>::LDS))
+#define SET(NKV)          \
+    SET1(NKV, 8, false);  \
+    SET1(NKV, 4, false);  \
+    SET1(NKV, 8, true);   \
+    SET1(NKV, 4, true)
     FBA_NK_DISPATCH(c.L.nk, SET);
 #undef SET
+#undef SET1
     return FBA_OK;
 }
 
@@ -1708,12 +1777,52 @@ int launch_residuals(Ctx& c) {
     const Layout& L = c.L;
     if (c.n_obs == 0) return FBA_OK;
     const int blocks = (int)((c.n_obs + 255) / 256);
-#define RS(NKV)                                                                                                \
-    k_residuals<NKV><<<blocks, 256, 0, c.stream>>>(c.d_J, c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie,        \
-                                                   c.d_delta, c.d_xfull, c.d_res, c.d_res + 2 * c.n_obs,       \
-                                                   c.d_part, c.n_obs, L.u_c, L.n_img, px_of(c), py_of(c))
+#define RS_ARGS                                                                                              \
+    c.d_J, c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_delta, c.d_xfull, c.d_res, c.d_res + 2 * c.n_obs, \
+        c.d_part, c.n_obs, L.u_c, L.n_img, px_of(c), py_of(c), c.d_seff, c.d_weff
+#define RS(NKV)                                                         \
+    if (c.whiten_on())                                                  \
+        k_residuals<NKV, true><<<blocks, 256, 0, c.stream>>>(RS_ARGS);  \
+    else                                                                \
+        k_residuals<NKV, false><<<blocks, 256, 0, c.stream>>>(RS_ARGS)
     FBA_NK_DISPATCH(L.nk, RS);
 #undef RS
+#undef RS_ARGS
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+// fba_set_weights: PHO order -> local order, with the square root the kernels whiten by
+__global__ __launch_bounds__(256) void k_set_weights(const double* __restrict__ wpho, const int64_t* __restrict__ obs_pho,
+                                                     int64_t n_obs, double* __restrict__ sw) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= n_obs) return;
+    const int64_t i = obs_pho[o];
+    sw[2 * o] = sqrt(wpho[2 * i]);
+    sw[2 * o + 1] = sqrt(wpho[2 * i + 1]);
+}
+
+// fba_get_weights: k_residuals' effective weights, local order -> PHO order (the caller zeroes wpho first:
+// another rank's rows stay 0)
+__global__ __launch_bounds__(256) void k_get_weights(const double* __restrict__ weff, const int64_t* __restrict__ obs_pho,
+                                                     int64_t n_obs, double* __restrict__ wpho) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= n_obs) return;
+    const int64_t i = obs_pho[o];
+    wpho[2 * i] = weff[2 * o];
+    wpho[2 * i + 1] = weff[2 * o + 1];
+}
+
+int launch_set_weights(Ctx& c, const double* d_wpho) {
+    if (c.n_obs == 0) return FBA_OK;
+    k_set_weights<<<(unsigned)((c.n_obs + 255) / 256), 256, 0, c.stream>>>(d_wpho, c.d_obs_pho, c.n_obs, c.d_sw);
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+int launch_get_weights(Ctx& c, double* d_wpho) {
+    if (c.n_obs == 0) return FBA_OK;
+    k_get_weights<<<(unsigned)((c.n_obs + 255) / 256), 256, 0, c.stream>>>(c.d_weff, c.d_obs_pho, c.n_obs, d_wpho);
     FBA_HIP(hipGetLastError());
     return FBA_OK;
 }

@@ -282,10 +282,13 @@ __global__ __launch_bounds__(256) void k_rel_ctl(RelMat M, const double* __restr
             nullptr, nullptr, nullptr, q + 2 * o);
 }
 
-// r = 1 - p q, w = v / (sigma sqrt(r)) (0 where r < 1e-10), local observation o -> PHO row obs_pho[o]
+// r = 1 - p q, w = v / (sigma sqrt(r)) (0 where r < 1e-10), local observation o -> PHO row obs_pho[o].  With
+// per-observation weights / a robust loss (seff: k_lin_point's s, else nullptr) q comes from whitened rows, so
+// r needs nothing, and the standardised residual is that of the whitened v: w = v s / (sigma sqrt(r)) (v is raw)
 __global__ __launch_bounds__(256) void k_rel_finish(const double* __restrict__ q, const double* __restrict__ v,
                                                     const int64_t* __restrict__ obs_pho, int64_t n_obs, double sx,
-                                                    double sy, double* __restrict__ red, double* __restrict__ wst) {
+                                                    double sy, const double* __restrict__ seff,
+                                                    double* __restrict__ red, double* __restrict__ wst) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= n_obs) return;
     const int64_t i = obs_pho[o];
@@ -294,7 +297,8 @@ __global__ __launch_bounds__(256) void k_rel_finish(const double* __restrict__ q
         const double s = m ? sy : sx;
         const double r = 1.0 - q[2 * o + m] / (s * s);
         red[2 * i + m] = r;
-        wst[2 * i + m] = r < 1e-10 ? 0.0 : v[2 * o + m] / (s * sqrt(r));
+        const double vm = seff ? v[2 * o + m] * seff[2 * o + m] : v[2 * o + m];
+        wst[2 * i + m] = r < 1e-10 ? 0.0 : vm / (s * sqrt(r));
     }
 }
 
@@ -331,7 +335,8 @@ int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d
     }
     FBA_HIP(hipGetLastError());
     k_rel_finish<<<(unsigned)((c.n_obs + 255) / 256), 256, 0, c.stream>>>(d_q, c.d_res, c.d_obs_pho, c.n_obs,
-                                                                         c.set.meas_std_x, c.set.meas_std_y, d_red, d_wst);
+                                                                         c.set.meas_std_x, c.set.meas_std_y,
+                                                                         c.whiten_on() ? c.d_seff : nullptr, d_red, d_wst);
     FBA_HIP(hipGetLastError());
     return FBA_OK;
 }

@@ -22,6 +22,7 @@ VERSION = "fba_amd 1 (MI355X HIP path)"
 MDB_DELTA0 = 4.13   # Baarda's non-centrality parameter for alpha0 = 0.1 %, beta0 = 80 % (write_rel's mdb)
 W_CRITICAL = 3.29   # two-sided 0.1 % point of the standard normal distribution (write_rel's flag)
 R_MIN = 1e-10       # below it an observation cannot be checked (fba_reliability reports w = 0)
+WGT_FLAG = 0.5      # write_wgt stars a row with an effective weight below it
 PRODUCER = "fba_amd, the MI355X-native HIP implementation (not the MATLAB reference)"
 
 
@@ -332,3 +333,36 @@ def write_rel(path, data, res):
             flag = "*" if max(abs(w[i, 0]), abs(w[i, 1])) > W_CRITICAL else ""
             fh.write("\t".join([data.pho_target[i], data.pho_image[i]]
                                + [_cell(v) for v in (r[i, 0], r[i, 1], w[i, 0], w[i, 1], mdb[0], mdb[1])] + [flag]) + "\n")
+
+
+def write_wgt(path, data, res):
+    """The weight table <Output_Filename stem>.wgt (no reference counterpart), written when per-observation
+    weights or a robust loss are in force; tab-delimited in write_rsd's style: PHO row (1-based, the line of
+    the .pho file), targetID, imageID, effective weight x, y (fba_get_weights: user weight x loss factor at the
+    last linearisation), flag per image point; flag is * where either weight is below WGT_FLAG."""
+    if res.weights is None:
+        raise ValueError("write_wgt: the adjustment carries no weights (adjust(..., weights= / robust=))")
+    w = np.asarray(res.weights, dtype=np.float64).reshape(-1, 2)
+    if len(w) != data.n_pts:
+        raise ValueError("write_wgt: weights must have 2*n_pts entries")
+    with open(path, "w") as fh:
+        for i in range(data.n_pts):
+            flag = "*" if min(w[i, 0], w[i, 1]) < WGT_FLAG else ""
+            fh.write("\t".join([str(i + 1), data.pho_target[i], data.pho_image[i], _cell(w[i, 0]), _cell(w[i, 1]), flag])
+                     + "\n")
+
+
+def read_wgt(path):
+    """write_wgt's table back: (rows, targetIDs, imageIDs, weights (n_pts, 2), flagged (n_pts) bool)."""
+    rows, tgt, img, w, flag = [], [], [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if len(c) != 6:
+                raise ValueError(f"read_wgt: {path}: expected 6 tab-separated columns, got {len(c)}")
+            rows.append(int(c[0]))
+            tgt.append(c[1])
+            img.append(c[2])
+            w.append((float(c[3]), float(c[4])))
+            flag.append(c[5] == "*")
+    return rows, tgt, img, np.array(w, dtype=np.float64).reshape(-1, 2), np.array(flag, dtype=bool)

@@ -238,6 +238,34 @@ int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr);
 int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr,
                     double* redundancy /*[2*n_pts]*/, double* wstat /*[2*n_pts]*/);
 
+/* Per-observation weights and robust loss (no reference counterpart: main.m:397-402 gives every observation
+ * the weight 1 / Meas_std^2).  Both setters may be called at any point between iterations (not between
+ * fba_solve_update_async and fba_solve_finish); both invalidate the last linearisation and the factor of the last
+ * solve, so fba_residuals, fba_covariance and fba_reliability return FBA_ERR_ARG until the next iteration.  The
+ * linearising kernels scale an observation's Jacobian row and misclosure by s = sqrt(weight x loss factor), so
+ * the normal equations, the covariance and the reliability quantities all carry the weight matrix
+ * P = diag(s^2 / Meas_std^2); fba_residuals reports v and the RSD rows in pixels (un-scaled), RMSx / RMSy from
+ * them, and v'Pv, sigma02 with the weights in.  fba_build_awg returns the raw A and w as before.
+ *
+ * fba_set_weights (no reference counterpart): weight [2*n_pts], PHO order, x y interleaved like v, multiplies
+ *   the a-priori weight: p_i = weight_i / Meas_std^2 (Meas_std_y^2 for y).  NULL restores all 1, and an array of
+ *   all 1 is taken as NULL (the unweighted kernels run, bit for bit a context that never had weights).  Every entry
+ *   must be finite and > 0 (FBA_ERR_ARG otherwise, checked on the host before anything else happens): an exact
+ *   0 is refused because the raw residual is recovered by division; a value such as 1e-12 excludes a
+ *   measurement.  With world > 1 every rank passes the full-length array and keeps its own observations'.
+ * fba_set_loss (no reference counterpart): loss = FBA_LOSS_*, k > 0 and finite in units of sigma (ignored for
+ *   FBA_LOSS_NONE).  Per image point t^2 = p_x w0^2 + p_y w1^2 from the misclosures at the linearisation point
+ *   (user weights included); both rows of the point are down-weighted by  Huber: 1 (t <= k), k / t   Cauchy:
+ *   1 / (1 + t^2 / k^2), re-evaluated inside every linearisation (IRLS).  Set it after the L2 iterations have
+ *   converged: at poor starting values every misclosure is large and everything would be down-weighted.
+ * fba_get_weights (no reference counterpart): weight [2*n_pts] receives the effective weights of the last
+ *   linearisation, user weight x loss factor (all 1 with neither set); same preconditions as fba_residuals.
+ *   With world > 1 the entries of other ranks' observations are 0 (the ranks' outputs sum to the whole). */
+enum { FBA_LOSS_NONE = 0, FBA_LOSS_HUBER = 1, FBA_LOSS_CAUCHY = 2 };
+int fba_set_weights(fba_ctx* ctx, const double* weight /*[2*n_pts], PHO order, x y interleaved; NULL: all 1*/);
+int fba_set_loss(fba_ctx* ctx, int32_t loss, double k);
+int fba_get_weights(fba_ctx* ctx, double* weight /*[2*n_pts]*/);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
