@@ -7,6 +7,9 @@
     ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
                                                of sigma (default: the 95 %-efficiency constants, huber 1.345,
                                                cauchy 2.385); also writes the .wgt table (report.write_wgt)
+    ... --priors                               (either command) the folder's .pri table, rows `<unknown name>
+                                               <value> <std>`, as prior observations of unknowns; also writes
+                                               the .prr table (report.write_prr)
 """
 import sys
 

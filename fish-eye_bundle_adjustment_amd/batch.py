@@ -47,17 +47,17 @@ def find_folders(folder, exts=EXTS, log=print):
     return out
 
 
-def batch_run(paths, device=0, robust=None, robust_k=None):
+def batch_run(paths, device=0, robust=None, robust_k=None, priors=False):
     """BatchRun.m:42-66: every data folder under the selected paths through main(folder, false);
     stops at the first folder whose main() fails.  Returns the list of (folder, main_error).
-    robust / robust_k: the robust loss of bundle.adjust, for every folder."""
+    robust / robust_k: the robust loss of bundle.adjust, for every folder; priors: every folder's .pri table."""
     from .bundle import main
     folders = []
     for p in paths:
         folders.extend(find_folders(p))
     done = []
     for f in folders:
-        err = main(f, False, device=device, **_robust_kw(robust, robust_k))
+        err = main(f, False, device=device, **_robust_kw(robust, robust_k), **_priors_kw(priors))
         done.append((f, err))
         if err == 1:
             break
@@ -67,6 +67,16 @@ def batch_run(paths, device=0, robust=None, robust_k=None):
 def _robust_kw(robust, robust_k):
     """main()'s keywords for a robust loss; none without one, so the call is the one it was"""
     return {"robust": robust, "robust_k": robust_k} if robust else {}
+
+
+def _priors_kw(priors):
+    """main()'s keyword for the .pri table; none without it, so the call is the one it was"""
+    return {"priors": True} if priors else {}
+
+
+def parse_priors(args):
+    """--priors anywhere in args -> (args without it, True / False): use the folder's .pri table"""
+    return [a for a in args if a != "--priors"], "--priors" in args
 
 
 def parse_robust(args):
@@ -99,23 +109,25 @@ def parse_robust(args):
 
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
-    anywhere after the folder (a --robust option is parse_robust's)"""
-    args = parse_robust(args)[0]
+    anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors')"""
+    args = parse_priors(parse_robust(args)[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--robust LOSS[:k]] | batch <folder>... "
-         "[--robust LOSS[:k]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, re-weighted at "
-         "every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber 1.345, cauchy "
-         "2.385; writes the .wgt table")
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--robust LOSS[:k]] [--priors] | batch <folder>... "
+         "[--robust LOSS[:k]] [--priors]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
+         "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
+         "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
+         "<std> per row) as prior observations of unknowns;\n      writes the .prr table")
 
 
 def cli(argv=None):
-    """python -m fba_cli main <folder> [plot] [--reliability] [--robust LOSS[:k]] | batch <folder>...
-    [--robust LOSS[:k]]   (main(folder, plot) / BatchRun.m); LOSS huber (k = 1.345) or cauchy (k = 2.385)"""
+    """python -m fba_cli main <folder> [plot] [--reliability] [--robust LOSS[:k]] [--priors] | batch <folder>...
+    [--robust LOSS[:k]] [--priors]   (main(folder, plot) / BatchRun.m); LOSS huber (k = 1.345) or cauchy (k = 2.385)"""
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
+        argv, priors = parse_priors(argv)
         argv, robust, robust_k = parse_robust(argv)
     except ValueError as e:
         print(f"Error: {e}")
@@ -124,9 +136,9 @@ def cli(argv=None):
     if len(argv) >= 2 and argv[0] == "main":
         from .bundle import main
         folder, plot, reliability = parse_main(argv[1:])
-        return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k))
+        return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors))
     if len(argv) >= 2 and argv[0] == "batch":
-        done = batch_run(argv[1:], **_robust_kw(robust, robust_k))
+        done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors))
         return 1 if any(e for _, e in done) else 0
     print(USAGE)
     return 2

@@ -81,10 +81,41 @@ class Adjustment:
     redundancy: np.ndarray = None  # (2 n_pts) redundancy numbers, PHO order, x y interleaved (reliability=True)
     wstat: np.ndarray = None       # (2 n_pts) standardised residuals w = v / (sigma sqrt(r))
     weights: np.ndarray = None     # (2 n_pts) effective weights, user weight x loss factor (weights= / robust=)
+    # prior observations of unknowns (priors=): index into xhat, observed value, std (xhat's units), the residual
+    # v = xhat[index] - value, and with a covariance the redundancy number r = 1 - cx_diag[index] / (sigma02 std^2)
+    # and the test statistic w = v / (std sqrt(r)), 0 where r < report.R_MIN
+    prior_index: np.ndarray = None
+    prior_value: np.ndarray = None
+    prior_sigma: np.ndarray = None
+    prior_v: np.ndarray = None
+    prior_r: np.ndarray = None
+    prior_w: np.ndarray = None
+
+
+def _priors_of(data, priors):
+    """adjust()'s priors argument -> (index, value, sigma) or None; True means the folder's .pri table"""
+    if priors is None or priors is False:
+        return None
+    if priors is True:
+        if getattr(data, "priors_error", ""):
+            raise IngestError(data.priors_error)
+        if getattr(data, "priors", None) is None:
+            raise IngestError(f"priors requested but there is no .pri file in {data.folder}")
+        return data.priors
+    return priors
+
+
+def prior_statistics(sigma02, cx_diag, index, sigma, v):
+    """A prior's own redundancy number r = 1 - cx_diag[index] / (sigma02 sigma^2) -- 1 - p (a Cx a') of its unit
+    row, from the final Cx's diagonal -- and its test statistic w = v / (sigma sqrt(r)), 0 where r < 1e-10
+    (host arithmetic on fba_covariance's output; fba_reliability's convention for an uncheckable observation)"""
+    r = 1.0 - np.asarray(cx_diag)[index] / (sigma02 * sigma ** 2)
+    ok = r >= 1e-10
+    return r, np.where(ok, v / (sigma * np.sqrt(np.where(ok, r, 1.0))), 0.0)
 
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
-           reliability=False) -> Adjustment:
+           reliability=False, priors=None) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -95,9 +126,15 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     iterates with L2 to the reference's stopping rule -- at the starting values every misclosure is large and a
     loss would down-weight everything -- then sets the loss and continues under the same threshold and the
     remaining Iteration_Cap.  Residuals, sigma0^2, covariance and reliability are those of the final,
-    re-weighted state; Adjustment.weights holds the effective weights."""
+    re-weighted state; Adjustment.weights holds the effective weights.
+
+    priors (no reference counterpart): None, True (the folder's .pri table, data.priors) or (index, value, sigma)
+    -- prior observations of unknowns, index into xhat, value and standard deviation in xhat's units
+    (fba_create_priors).  sigma0^2 then counts them (v'Pv and the degrees of freedom), and Adjustment.prior_*
+    carry their residuals, redundancy numbers and test statistics."""
     t0 = time.perf_counter()
-    ctx = capi.Context(data.pack(), capi.make_settings(data.settings), device=device, verbose=verbose)
+    pri = _priors_of(data, priors)
+    ctx = capi.Context(data.pack(), capi.make_settings(data.settings), device=device, verbose=verbose, priors=pri)
     try:
         if weights is not None:
             ctx.set_weights(weights)
@@ -119,11 +156,17 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
             cxd, corr, red, wst = ctx.reliability(st[3])
         else:
             cxd, corr = ctx.covariance(st[3]) if covariance else (None, None)
+        pkw = {}
+        if ctx.priors is not None:
+            pi, pl, ps = ctx.priors
+            pv = ctx.get_priors()[0]
+            pr, pw = prior_statistics(st[3], cxd, pi, ps, pv) if cxd is not None else (None, None)
+            pkw = dict(prior_index=pi, prior_value=pl, prior_sigma=ps, prior_v=pv, prior_r=pr, prior_w=pw)
     finally:
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff)
+                      redundancy=red, wstat=wst, weights=eff, **pkw)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -139,19 +182,25 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_rel(os.path.join(folder, name + ".rel"), data, res)
     if res.weights is not None:
         report.write_wgt(os.path.join(folder, name + ".wgt"), data, res)
+    if res.prior_index is not None:
+        report.write_prr(os.path.join(folder, name + ".prr"), data, res)
     return out
 
 
-def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None) -> int:
+def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
+         priors=False) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
-    adjust()'s robust loss; the .wgt table (report.write_wgt) is written too."""
+    adjust()'s robust loss; the .wgt table (report.write_wgt) is written too.  priors=True: the folder's .pri
+    table as prior observations of unknowns (io.read_pri; without the file main returns 1); the .prr table
+    (report.write_prr) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
         data = load_folder(folder, project_dir=None if folder == project_dir else project_dir)
-        res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k)
+        res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k,
+                     **({"priors": True} if priors else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:
         print(f"Error: {e}")

@@ -23,7 +23,7 @@ NK_MAX = 8
 # every symbol include/fba.h declares
 EXPORTS = (
     "fba_last_error", "fba_abi_version", "fba_count_unknowns", "fba_partition", "fba_image_order", "fba_create",
-    "fba_destroy", "fba_solve_mode", "fba_buildxhat", "fba_set_xhat", "fba_get_xhat", "fba_build_awg",
+    "fba_create_priors", "fba_get_priors", "fba_destroy", "fba_solve_mode", "fba_buildxhat", "fba_set_xhat", "fba_get_xhat", "fba_build_awg",
     "fba_accumulate", "fba_reduce_buffer", "fba_synchronize", "fba_solve_update", "fba_solve_update_async",
     "fba_deltasum_device", "fba_solve_finish", "fba_step", "fba_adjust",
     "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability",
@@ -57,6 +57,26 @@ class Options(C.Structure):
                 ("stream", C.c_void_p), ("split", C.c_int32)]
 
 
+class Priors(C.Structure):
+    _fields_ = [("n", C.c_int64), ("index", C.c_void_p), ("value", C.c_void_p), ("sigma", C.c_void_p)]
+
+
+def pack_priors(priors):
+    """(index, value, sigma) -> (fba_priors, the arrays it points into), or (None, None) for None / no rows.
+    Shapes only: the values are checked by fba_create_priors, on the host, before it touches the GPU."""
+    if priors is None:
+        return None, None
+    index, value, sigma = priors
+    index = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+    value = np.ascontiguousarray(value, dtype=np.float64).reshape(-1)
+    sigma = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+    if not (index.size == value.size == sigma.size):
+        raise ValueError("priors: index, value and sigma must have the same length")
+    if index.size == 0:
+        return None, None
+    return Priors(index.size, ptr(index).value, ptr(value).value, ptr(sigma).value), (index, value, sigma)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is not built: run `make -C {os.path.join(_HERE, 'csrc')}` "
@@ -70,6 +90,8 @@ def _load():
         "fba_partition": ([P, I, P, P], C.c_int),
         "fba_image_order": ([P, P, P], C.c_int),
         "fba_create": ([P, P, P, P], C.c_int),
+        "fba_create_priors": ([P, P, P, P, P], C.c_int),
+        "fba_get_priors": ([P, P, P, P], C.c_int),
         "fba_destroy": ([P], None),
         "fba_solve_mode": ([P, P], C.c_int),
         "fba_buildxhat": ([P, P, P], C.c_int),
@@ -163,13 +185,20 @@ class Context:
     """One device-resident adjustment (one GPU / one rank)."""
 
     def __init__(self, packed: PackedProblem, settings: Settings, device=0, rank=0, world=1, stream=None,
-                 verbose=False, split=False):
+                 verbose=False, split=False, priors=None):
+        """priors: (index, value, sigma) -- prior observations of unknowns, index into the reference-layout xhat
+        (fba_create_priors); None, or no rows, is fba_create."""
         self.packed = packed
         self.settings = settings
         self.world = world
         opts = Options(device, rank, world, int(verbose), stream, int(bool(split)))
         h = C.c_void_p()
-        check(lib.fba_create(C.byref(packed.struct), C.byref(settings), C.byref(opts), C.byref(h)))
+        pr, self.priors = pack_priors(priors)
+        if pr is None:
+            check(lib.fba_create(C.byref(packed.struct), C.byref(settings), C.byref(opts), C.byref(h)))
+        else:
+            check(lib.fba_create_priors(C.byref(packed.struct), C.byref(settings), C.byref(opts), C.byref(pr),
+                                        C.byref(h)))
         self.h = h
         # the solve libfba runs: a split request falls back to the replicated solve when the block
         # pattern cannot be cut (fba_solve_mode)
@@ -337,6 +366,14 @@ class Context:
         w = np.zeros(max(2 * self.packed.n_pts, 1))
         check(lib.fba_get_weights(self.h, ptr(w)))
         return w[: 2 * self.packed.n_pts]
+
+    def get_priors(self):
+        """fba_get_priors: (resid, vtpv) -- the priors' residuals xhat[index] - value at the device xhat, in the
+        order they were given (0 for the priors another rank adds), and this rank's sum of p v^2"""
+        n = 0 if self.priors is None else self.priors[0].size
+        resid, vtpv = np.zeros(max(n, 1)), C.c_double()
+        check(lib.fba_get_priors(self.h, None, ptr(resid), C.byref(vtpv)))
+        return resid[:n], vtpv.value
 
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""

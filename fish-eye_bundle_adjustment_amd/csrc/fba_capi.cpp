@@ -168,7 +168,8 @@ static void destroy(Ctx* c) {
                     c->d_acc, c->d_ppart, c->d_U, c->d_ipart, c->d_cpart, c->d_cseg, c->d_bscr, c->d_gblk, c->d_lrprof, c->d_ptrace, c->d_gpairs, c->d_red, c->d_xfull, c->d_xlin, c->d_delta, c->d_img_tab, c->d_cam_tab, c->d_G, c->d_J, c->d_WT,
                     c->d_pt_tab, c->d_P, c->d_flags, c->d_S, c->d_X, c->d_dinv, c->d_linv, c->d_scal, c->d_part, c->d_res, c->d_caminfo,
                     c->d_active, c->d_counted, c->d_obs_pho, c->d_sched, c->d_gpt, c->d_gcu, c->d_gug, c->d_xpart,
-                    c->d_kpart, c->d_bown, c->d_rown, c->d_topdiag, c->d_sw, c->d_seff, c->d_weff};
+                    c->d_kpart, c->d_bown, c->d_rown, c->d_topdiag, c->d_sw, c->d_seff, c->d_weff,
+                    c->d_pc_idx, c->d_pc_val, c->d_gprior, c->d_pr_idx, c->d_pr_val, c->d_pr_out, c->d_pr_part};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     for (auto& w : c->ws)
@@ -185,7 +186,40 @@ static void destroy(Ctx* c) {
     delete c;
 }
 
-static int create(const fba_problem* p, const fba_settings* s, const fba_options* o, Ctx** out) {
+// fba_create_priors' list against the u unknowns of the reference layout (host only)
+static int check_priors(const fba_priors* pr, int64_t u) {
+    if (pr->n < 0 || !pr->index || !pr->value || !pr->sigma) { set_error("fba_create_priors: negative n or NULL array"); return FBA_ERR_ARG; }
+    char buf[200];
+    std::vector<int64_t> seen(pr->index, pr->index + pr->n);
+    for (int64_t j = 0; j < pr->n; ++j) {
+        if (pr->index[j] < 0 || pr->index[j] >= u) {
+            snprintf(buf, sizeof buf, "fba_create_priors: index[%ld] = %ld is outside [0, %ld)", (long)j, (long)pr->index[j], (long)u);
+            set_error(buf);
+            return FBA_ERR_ARG;
+        }
+        if (!std::isfinite(pr->value[j])) {
+            snprintf(buf, sizeof buf, "fba_create_priors: value[%ld] = %g must be finite", (long)j, pr->value[j]);
+            set_error(buf);
+            return FBA_ERR_ARG;
+        }
+        if (!std::isfinite(pr->sigma[j]) || !(pr->sigma[j] > 0.0)) {
+            snprintf(buf, sizeof buf, "fba_create_priors: sigma[%ld] = %g must be finite and > 0", (long)j, pr->sigma[j]);
+            set_error(buf);
+            return FBA_ERR_ARG;
+        }
+    }
+    std::sort(seen.begin(), seen.end());
+    const auto dup = std::adjacent_find(seen.begin(), seen.end());
+    if (dup != seen.end()) {
+        snprintf(buf, sizeof buf, "fba_create_priors: duplicate index %ld (one prior per unknown)", (long)*dup);
+        set_error(buf);
+        return FBA_ERR_ARG;
+    }
+    return FBA_OK;
+}
+
+// pr: prior observations of unknowns, or nullptr (fba_create)
+static int create(const fba_problem* p, const fba_settings* s, const fba_options* o, const fba_priors* pr, Ctx** out) {
     int rc = check_settings(s);
     if (rc) return rc;
     rc = check_problem(p, s);
@@ -194,6 +228,16 @@ static int create(const fba_problem* p, const fba_settings* s, const fba_options
     opt.world = 1;
     if (o) opt = *o;
     if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world) { set_error("bad rank/world"); return FBA_ERR_ARG; }
+    if (pr && pr->n == 0) pr = nullptr;
+    if (pr) {
+        int64_t u = 0;
+        fba_count_unknowns(p, s, &u);
+        if ((rc = check_priors(pr, u))) return rc;
+        if (opt.world > 1 && opt.split) {
+            set_error("fba_create_priors: priors are not implemented for the subtree split (fba_options.split); use the replicated solve");
+            return FBA_ERR_UNSUPPORTED;
+        }
+    }
 
     Ctx* c = new Ctx();
     c->prob = *p;
@@ -306,8 +350,23 @@ static int create(const fba_problem* p, const fba_settings* s, const fba_options
         }
     // regular tie points (k_lin_reduce's chunks): one camera, <= CHUNK_OBS observations, at most one per
     // image; the others are "general" points (fba_general.hip) -- the reference accepts all of them
+    // a tie point that carries a prior is a general point too: its V and b take the prior's terms in
+    // k_gen_point (k_lin_reduce forms and factors V per chunk and knows no priors)
+    const int64_t ref_tie0 = (int64_t)L.u_img * L.n_img_ref + (int64_t)L.u_cam * L.n_cam;  // xhat index of the first tie unknown
+    std::vector<uint8_t> has_prior(L.n_tie, 0);
+    for (int64_t j = 0; pr && j < pr->n; ++j)
+        if (pr->index[j] >= ref_tie0) {
+            const int t = (int)((pr->index[j] - ref_tie0) / 3);
+            if (tie_obs[t].empty()) {
+                set_error("fba_create_priors: a prior on a tie point without observations");
+                destroy(c);
+                return FBA_ERR_UNSUPPORTED;
+            }
+            has_prior[t] = 1;
+        }
     auto is_general = [&](int t) {
         const std::vector<int64_t>& ob = tie_obs[t];
+        if (has_prior[t]) return true;
         if ((int64_t)ob.size() > CHUNK_OBS) return true;
         std::vector<int32_t> im;
         for (int64_t i : ob) {
@@ -780,6 +839,57 @@ static int create(const fba_problem* p, const fba_settings* s, const fba_options
     std::vector<int32_t> xoff(pt.size(), 0);
     for (size_t o = 0; o < pt.size(); ++o)
         if (pt[o] >= 0) xoff[o] = (int32_t)(L.u_c + 3 * (int64_t)lp_tie[pt[o]]);
+    // priors: the tables of the ones this rank adds -- camera-side on rank 0 (k_prior_cam), a tie point's on
+    // its owner (k_gen_point's per-point table), all of them for the residuals (k_prior_resid)
+    if (pr) {
+        c->n_prior = pr->n;
+        std::vector<int64_t> ref_to_full(L.u_ref, -1);
+        for (int64_t i = 0; i < L.u_full; ++i)
+            if (c->full_to_ref[i] >= 0) ref_to_full[c->full_to_ref[i]] = i;
+        std::vector<int32_t> gp_of(L.n_tie, -1);
+        for (size_t q = 0; q < gps.size(); ++q) gp_of[gps[q]] = (int32_t)q;
+        std::vector<int32_t> pc_idx;
+        std::vector<int64_t> pr_idx;
+        std::vector<double> pc_val, pr_val, gprior;
+        const int64_t cb = 6 * (int64_t)L.n_img;
+        const int stride = CAM_TAB_HDR + 3 * L.nk;  // Ctx::cam_tab_stride (set below)
+        for (int64_t j = 0; j < pr->n; ++j) {
+            const int64_t i = ref_to_full[pr->index[j]];
+            const double pw = 1.0 / (pr->sigma[j] * pr->sigma[j]);
+            if (i < L.u_c) {
+                if (opt.rank != 0) continue;
+                int so = -1;  // the distortion unknowns' scale in the camera table: rmax^(2j) for K_j, rmax^2 for P
+                if (i >= cb) {
+                    const int k = (int)((i - cb) / L.cw), q = (int)((i - cb) % L.cw);
+                    if (q >= 3 && q < 3 + L.nk) so = k * stride + CAM_TAB_HDR + L.nk + (q - 3);
+                    else if (q >= 3 + L.nk) so = k * stride + 6;
+                }
+                pc_idx.push_back((int32_t)i);
+                pc_idx.push_back(so);
+                pc_val.push_back(pw);
+                pc_val.push_back(pr->value[j]);
+            } else {
+                const int t = (int)((i - L.u_c) / 3), d = (int)((i - L.u_c) % 3);
+                if (gp_of[t] < 0) continue;  // another rank's point
+                if (gprior.empty()) gprior.assign(6 * gps.size(), 0.0);
+                gprior[6 * (size_t)gp_of[t] + d] = pw;
+                gprior[6 * (size_t)gp_of[t] + 3 + d] = pr->value[j];
+            }
+            pr_idx.push_back(i);
+            pr_idx.push_back(j);
+            pr_val.push_back(pw);
+            pr_val.push_back(pr->value[j]);
+        }
+        c->n_pcam = (int64_t)pc_idx.size() / 2;
+        c->n_pres = (int64_t)pr_idx.size() / 2;
+        if ((c->n_pcam > 0 && ((rc = upload(&c->d_pc_idx, pc_idx)) || (rc = upload(&c->d_pc_val, pc_val)))) ||
+            (!gprior.empty() && (rc = upload(&c->d_gprior, gprior))) ||
+            (c->n_pres > 0 && ((rc = upload(&c->d_pr_idx, pr_idx)) || (rc = upload(&c->d_pr_val, pr_val)))) ||
+            (rc = dalloc(&c->d_pr_out, (size_t)c->n_prior + 1)) || (rc = dalloc(&c->d_pr_part, (size_t)(c->n_pres + 255) / 256))) {
+            destroy(c);
+            return rc;
+        }
+    }
     if ((rc = upload(&c->d_xoff, xoff)) || (rc = dalloc(&c->d_lrt, 2)) ||
         hipMemset(c->d_lrt, 0, 2 * sizeof(unsigned)) != hipSuccess) {
         destroy(c);
@@ -915,7 +1025,8 @@ static int accumulate_body(Ctx* c) {
     // general tie points: their Jacobian rows, point tables and partials (ahead of the reductions)
     if ((rc = launch_gen_tables(*c, nullptr)) || (rc = launch_gen_keys(*c))) return rc;
     mark(c, 2);
-    if ((rc = launch_accumulate(*c)) || (rc = launch_gen_reduce(*c))) return rc;
+    // the camera-side priors behind the reductions' stores of the summed partials, ahead of the pack and the border
+    if ((rc = launch_accumulate(*c)) || (rc = launch_gen_reduce(*c)) || (rc = launch_prior_cam(*c))) return rc;
     if (c->d_lrprof) {  // FBA_LR_PROFILE: per-phase averages of k_lin_reduce (us)
         std::vector<uint64_t> tp(8 * c->n_chunks_lr);
         FBA_HIP(hipMemcpyAsync(tp.data(), c->d_lrprof, sizeof(uint64_t) * tp.size(), hipMemcpyDeviceToHost, c->stream));
@@ -1258,9 +1369,36 @@ int fba_create(const fba_problem* p, const fba_settings* s, const fba_options* o
     if (!out) { set_error("out is NULL"); return FBA_ERR_ARG; }
     *out = nullptr;
     Ctx* c = nullptr;
-    int rc = create(p, s, o, &c);
+    int rc = create(p, s, o, nullptr, &c);
     if (rc) return rc;
     *out = reinterpret_cast<fba_ctx*>(c);
+    return FBA_OK;
+}
+
+int fba_create_priors(const fba_problem* p, const fba_settings* s, const fba_options* o, const fba_priors* pr,
+                      fba_ctx** out) {
+    if (!out) { set_error("out is NULL"); return FBA_ERR_ARG; }
+    *out = nullptr;
+    Ctx* c = nullptr;
+    int rc = create(p, s, o, pr, &c);
+    if (rc) return rc;
+    *out = reinterpret_cast<fba_ctx*>(c);
+    return FBA_OK;
+}
+
+int fba_get_priors(fba_ctx* ctx, int64_t* n, double* resid, double* vtpv) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_get_priors: NULL context"); return FBA_ERR_ARG; }
+    if (n) *n = c->n_prior;
+    if (vtpv) *vtpv = 0.0;
+    if (c->n_prior == 0 || (!resid && !vtpv)) return FBA_OK;
+    int rc;
+    if ((rc = launch_prior_resid(*c))) return rc;
+    std::vector<double> out((size_t)c->n_prior + 1);
+    FBA_HIP(hipMemcpyAsync(out.data(), c->d_pr_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    if (resid) std::copy(out.begin(), out.end() - 1, resid);
+    if (vtpv) *vtpv = out.back();
     return FBA_OK;
 }
 
@@ -1461,8 +1599,13 @@ int fba_residuals(fba_ctx* ctx, double* v, double* rsd, double* stats) {
     }
     double sx = 0, sy = 0, sp = 0;
     for (int b = 0; b < nblk; ++b) { sx += part[3 * b]; sy += part[3 * b + 1]; sp += part[3 * b + 2]; }
+    if (stats && c->n_prior > 0) {  // the priors' rows: v'Pv gains sum p v^2, the divisor their count
+        double pv = 0.0;
+        if ((rc = fba_get_priors(ctx, nullptr, nullptr, &pv))) return rc;
+        sp += pv;
+    }
     if (stats) {
-        const double nu = (double)(2 * c->n_pts - c->L.u_ref);
+        const double nu = (double)(2 * c->n_pts + c->n_prior - c->L.u_ref);
         if (c->opt.world == 1) {
             const double rx = std::sqrt(sx / (double)c->n_pts), ry = std::sqrt(sy / (double)c->n_pts);
             stats[0] = rx; stats[1] = ry; stats[2] = std::sqrt(rx * rx + ry * ry);

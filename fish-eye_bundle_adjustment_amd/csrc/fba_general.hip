@@ -54,10 +54,16 @@ __device__ __forceinline__ void tri_ab(int q, int& a, int& b) {
     b = q;
 }
 
-template <int NK>
+// PR: the points' prior observations (fba_create_priors): unit rows on the point's own coordinates, so V_dd += p_d
+// and b_d += p_d (X_d - l_d) after the wave sums, from prior [n_gp][6] (p0 p1 p2 l0 l1 l2, p = 0: none) and the
+// point's coordinates at the linearisation point x; everything downstream reads V^-1, R, rb, vb from the table.
+// Without priors the PR = false instantiation runs: the kernel as it was
+template <int NK, bool PR>
 __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, const int32_t* __restrict__ A,
                                                   const GenPlan g, double* __restrict__ gpt, double* __restrict__ gcu,
-                                                  double* __restrict__ gug, double px, double py) {
+                                                  double* __restrict__ gug, double px, double py,
+                                                  const double* __restrict__ prior, const double* __restrict__ x,
+                                                  const int32_t* __restrict__ lp_tie, int64_t u_c) {
     using Q = GL<NK>;
     constexpr int CW = Q::CW, NJ = Q::NJ, JS = Q::JS, GC = Q::GC;
     const int q = blockIdx.x, l = threadIdx.x;
@@ -78,6 +84,12 @@ __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, 
     }
 #pragma unroll
     for (int m = 0; m < 9; ++m) V[m] = wave_sum(V[m]);
+    if constexpr (PR) {
+        const double* pr = prior + (int64_t)q * 6;
+        const double* X = x + u_c + 3 * (int64_t)lp_tie[g.lp0 + q];
+        V[0] += pr[0]; V[3] += pr[1]; V[5] += pr[2];
+        V[6] += pr[0] * (X[0] - pr[3]); V[7] += pr[1] * (X[1] - pr[4]); V[8] += pr[2] * (X[2] - pr[5]);
+    }
     const double V00 = V[0], V01 = V[1], V02 = V[2], V11 = V[3], V12 = V[4], V22 = V[5];
     const double b0 = V[6], b1 = V[7], b2 = V[8];
     // symmetric 3x3 inverse (adjugate) and R = L^-T of V = L L' (as k_lin_reduce)
@@ -418,8 +430,15 @@ int launch_gen_tables(Ctx& c, const double* x) {
     int rc;
     if ((rc = launch_linearize_range(c, x, c.n_chunks_lr, c.n_chunks))) return rc;  // J of the general observations
     const double px = 1.0 / (c.set.meas_std_x * c.set.meas_std_x), py = 1.0 / (c.set.meas_std_y * c.set.meas_std_y);
-#define GP(NKV) k_gen_point<NKV><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(c.d_J, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, px, py)
+    const double* xp = x ? x : c.d_xfull;
+#define GP_ARGS c.d_J, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, px, py, c.d_gprior, xp, c.d_lp_tie, c.L.u_c
+#define GP(NKV)                                                                 \
+    if (c.d_gprior)                                                             \
+        k_gen_point<NKV, true><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS); \
+    else                                                                        \
+        k_gen_point<NKV, false><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS)
     GEN_NK_DISPATCH(c.L.nk, GP);
+#undef GP_ARGS
 #undef GP
     FBA_HIP(hipGetLastError());
     return FBA_OK;

@@ -339,6 +339,18 @@ struct Ctx {
     double loss_k = 0.0;
     bool whiten_on() const { return weights_on || loss != 0; }
     Whiten whiten() const { return Whiten{weights_on ? d_sw : nullptr, loss, loss_k}; }
+    // prior observations of unknowns (fba_create_priors; constants of the context).  A prior is ADDED by one
+    // rank: image / camera unknowns by rank 0, a tie point's by its owner
+    int64_t n_prior = 0;             // all priors of the call
+    int64_t n_pcam = 0;              // camera-side priors this rank adds (k_prior_cam)
+    int32_t* d_pc_idx = nullptr;     // [n_pcam][2] row of S (= full-space index), cam_tab offset of its scale or -1
+    double* d_pc_val = nullptr;      // [n_pcam][2] p, l
+    double* d_gprior = nullptr;      // [n_gp][6] p0 p1 p2 l0 l1 l2 per general point (p = 0: none); nullptr: no tie prior
+    int64_t n_pres = 0;              // priors this rank adds, camera-side and tie (k_prior_resid)
+    int64_t* d_pr_idx = nullptr;     // [n_pres][2] full-space index, number of the prior in the caller's list
+    double* d_pr_val = nullptr;      // [n_pres][2] p, l
+    double* d_pr_out = nullptr;      // [n_prior + 1] residuals in the caller's order, then this rank's sum p v^2
+    double* d_pr_part = nullptr;     // [ceil(n_pres / 256)] block partials of p v^2
     double* h_pinned = nullptr;  // pinned host scratch (coherent, mapped: k_sum_parts writes scal[0..3] here,
                                  // then [4] = its running count of solves, scal[5])
     double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[4])
@@ -410,6 +422,8 @@ int launch_gen_reduce(Ctx& c);
 int launch_gen_backsub(Ctx& c);
 int launch_gen_cov(Ctx& c, const double* Z, const double* Wz, int nz, double* pdiag);
 int launch_accumulate(Ctx& c, bool zeroed = false);  // zero S (unless zeroed), image, pair, camera blocks
+int launch_prior_cam(Ctx& c);    // camera-side priors into S's diagonal and RHS row (after the reductions' stores)
+int launch_prior_resid(Ctx& c);  // prior residuals at d_xfull and their sum p v^2 -> d_pr_out
 int launch_border(Ctx& c);       // alpha, G G^T border, RHS rows
 int chol_setup(Ctx& c);
 int acc_setup(Ctx& c);            // kernel attributes of the accumulation kernels          // one-time kernel attributes, streams, events

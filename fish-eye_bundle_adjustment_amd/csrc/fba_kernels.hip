@@ -1442,6 +1442,72 @@ __global__ void k_sum_parts(const double* __restrict__ part, int n, double* __re
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// prior observations of unknowns (fba_create_priors; no reference counterpart).  Prior j adds the unit row
+// e_i with weight p and misclosure x_i - l; a distortion unknown's column is in scaled units
+// (BuildAwG.m:419-451), so its row entry is 1 / s with s = rmax^(2j) (K_j) or rmax^2 (P), read from the
+// camera table k_params wrote: S_ii += p / s^2, rhs_i += p (x_i - l) / s.
+// ------------------------------------------------------------------------------------------------
+// the camera-side priors (image and camera unknowns), one thread each: every prior has its own row of S,
+// and the reductions before this launch have stored that row's sums (k_red_blocks, k_red_cam, k_red_gen),
+// so each entry is one read-add-write by one thread -- no atomics, a fixed order
+__global__ __launch_bounds__(256) void k_prior_cam(const int32_t* __restrict__ idx, const double* __restrict__ val, int n,
+                                                   const double* __restrict__ xfull, const double* __restrict__ cam_tab,
+                                                   double* __restrict__ S, int64_t ld, int64_t n_pad) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t i = idx[2 * j];
+    const int so = idx[2 * j + 1];
+    const double p = val[2 * j], l = val[2 * j + 1];
+    const double is = so >= 0 ? 1.0 / cam_tab[so] : 1.0;
+    const double a = p * is;
+    S[i * ld + i] += a * is;
+    S[n_pad * ld + i] += a * (xfull[i] - l);
+}
+
+// the residuals v = x - l of the priors this rank adds, into the caller's order (out[number]), and the block
+// partials of p v^2; k_prior_vtpv adds the partials in order (k_sum_parts' pattern) into out[n_prior]
+__global__ __launch_bounds__(256) void k_prior_resid(const int64_t* __restrict__ idx, const double* __restrict__ val,
+                                                     int64_t n, const double* __restrict__ xfull, double* __restrict__ out,
+                                                     double* __restrict__ part) {
+    __shared__ double red[4];
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double a = 0.0;
+    if (j < n) {
+        const double v = xfull[idx[2 * j]] - val[2 * j + 1];
+        out[idx[2 * j + 1]] = v;
+        a = val[2 * j] * (v * v);
+    }
+    const double s = block_sum256(a, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void k_prior_vtpv(const double* __restrict__ part, int n, double* __restrict__ out) {
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += part[i];  // thread t: parts t, t + 256, ... in order
+    const double sum = block_sum256(a, red);
+    if (threadIdx.x == 0) *out = sum;
+}
+
+int launch_prior_cam(Ctx& c) {
+    if (c.n_pcam == 0) return FBA_OK;
+    k_prior_cam<<<(unsigned)((c.n_pcam + 255) / 256), 256, 0, c.stream>>>(c.d_pc_idx, c.d_pc_val, (int)c.n_pcam, c.d_xfull,
+                                                                         c.d_cam_tab, c.d_S, c.L.ld, c.L.n_pad);
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+int launch_prior_resid(Ctx& c) {
+    FBA_HIP(hipMemsetAsync(c.d_pr_out, 0, sizeof(double) * (size_t)(c.n_prior + 1), c.stream));
+    if (c.n_pres == 0) return FBA_OK;
+    const int nblk = (int)((c.n_pres + 255) / 256);
+    k_prior_resid<<<nblk, 256, 0, c.stream>>>(c.d_pr_idx, c.d_pr_val, c.n_pres, c.d_xfull, c.d_pr_out, c.d_pr_part);
+    k_prior_vtpv<<<1, 256, 0, c.stream>>>(c.d_pr_part, nblk, c.d_pr_out + c.n_prior);
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // residuals: v = J delta + w (main.m:569; delta = de-scaled last correction, as the reference),
@@ -1673,9 +1739,10 @@ __global__ __launch_bounds__(256) void k_zero_blocks(double* __restrict__ S, int
 }
 
 // the border weights read the image rows' diagonal of S: final at the end of the accumulation when no
-// general tie points (launch_gen_reduce) and no other rank (launch_pack / the split) add to S after it
+// general tie points (launch_gen_reduce), no camera-side prior (launch_prior_cam) and no other rank
+// (launch_pack / the split) add to S after it
 bool border_weights_in_accumulate(const Ctx& c) {
-    return c.n_chunks_lr > 0 && c.gen.n_gp == 0 && c.opt.world <= 1 && !c.sched.split;
+    return c.n_chunks_lr > 0 && c.gen.n_gp == 0 && c.n_pcam == 0 && c.opt.world <= 1 && !c.sched.split;
 }
 
 int launch_accumulate(Ctx& c, bool zeroed) {

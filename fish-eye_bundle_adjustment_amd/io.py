@@ -147,6 +147,11 @@ class Dataset:
     numCam: int
     numGCP: int
     CZE: list = field(default_factory=list)
+    # the optional <name>.pri table (read_pri): (index, value, sigma) in xhat's order and units, None without
+    # the file; used only on request (bundle.adjust(priors=True)).  A table that does not parse leaves its
+    # message in priors_error, raised by that request -- a run that does not ask is not touched by the file
+    priors: tuple = None
+    priors_error: str = ""
 
     @property
     def n_pts(self):
@@ -257,9 +262,47 @@ def load_folder(folder, project_dir=None):
         # main.m:397-399: no_std_y is set but the Meas_std_y field was never created -> rmfield fails
         raise IngestError("no Meas_std in the .cfg: the reference fails at main.m:399 "
                           "(rmfield of the absent Meas_std_y field)")
-    return Dataset(folder=folder, settings=s, pho_target=[r[0] for r in pho], pho_image=[r[1] for r in pho],
-                   xy=xy, img=img, cam=cam, tie=tie, xyz_fixed=xyz, EXT=EXT, INT=INT, TIE=TIE, CNT=CNT,
-                   numImg=numImg, numCam=numCam, numGCP=len(cnt_used), CZE=CZE)
+    ds = Dataset(folder=folder, settings=s, pho_target=[r[0] for r in pho], pho_image=[r[1] for r in pho],
+                 xy=xy, img=img, cam=cam, tie=tie, xyz_fixed=xyz, EXT=EXT, INT=INT, TIE=TIE, CNT=CNT,
+                 numImg=numImg, numCam=numCam, numGCP=len(cnt_used), CZE=CZE)
+    try:
+        pri = find_file(folder, ".pri", required=False)
+        if pri is not None:
+            ds.priors = read_pri(pri, ds)
+    except IngestError as e:
+        ds.priors_error = str(e)
+    return ds
+
+
+ANGLE_HEADS = ("w", "p", "k")  # omega, phi, kappa: degrees in the files (.ext, .pri), radians in xhat
+
+
+def read_pri(path, ds: Dataset):
+    """The prior-observation table <name>.pri (no reference counterpart): rows `<unknown name> <value> <std>`,
+    the name exactly as xhat_names gives it (Xc_<image>_<camera>, w_..., c_<camera>, k2_<camera>, X_<target>);
+    w / p / k values and their std in degrees, as in .ext.  -> (index, value, sigma) in xhat's order of rows
+    and units.  IngestError for a name that is not an estimated unknown, a name given twice, a std <= 0 or a
+    value / std that is not a finite number."""
+    pos = {}
+    for j, nm in enumerate(xhat_names(ds)):
+        pos.setdefault(nm, j)
+    index, value, sigma, seen = [], [], [], set()
+    for r in read_table(path):
+        if len(r) != 3:
+            raise IngestError(f"{path}: expected `<unknown name> <value> <std>`, got {' '.join(r)!r}")
+        name, val, std = r[0], _num(r[1]), _num(r[2])
+        if name not in pos:
+            raise IngestError(f"{path}: {name} is not an estimated unknown of this adjustment")
+        if name in seen:
+            raise IngestError(f"{path}: {name} is given twice")
+        if not (math.isfinite(val) and math.isfinite(std)) or not std > 0:
+            raise IngestError(f"{path}: {name}: the value must be a finite number and the std finite and > 0")
+        seen.add(name)
+        f = math.pi / 180 if name.split("_", 1)[0] in ANGLE_HEADS else 1.0
+        index.append(pos[name])
+        value.append(val * f)
+        sigma.append(std * f)
+    return (np.array(index, dtype=np.int64), np.array(value, dtype=np.float64), np.array(sigma, dtype=np.float64))
 
 
 def xhat_names(ds: Dataset):

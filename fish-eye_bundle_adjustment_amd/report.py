@@ -109,6 +109,9 @@ def write_out(path, data, res, seconds, version=VERSION, date=None):
     std = np.sqrt(np.maximum(cxd, 0.0)) if cxd is not None else np.full(len(xhat), np.nan)
     date = date or datetime.date.today().strftime("%d-%b-%Y")
     n = data.n
+    # prior observations of unknowns (no reference counterpart): counted as observations when they were used
+    n_prior = len(res.prior_index) if getattr(res, "prior_index", None) is not None else 0
+    prior_rows = [("Number of prior observations", num2str(n_prior))] if n_prior else []
     with open(path, "w") as fh:
         fh.write("Version: " + version)
         # main.m:637's title and author line, with this build named as the producer of the numbers below
@@ -137,11 +140,11 @@ def write_out(path, data, res, seconds, version=VERSION, date=None):
                 ("\\n", ""),
                 ("Number of image points", num2str(n // 2)),
                 ("Total number of observations", num2str(n)),
-                ("Number of Inner Constraints", num2str(7 * ic)),
+                ("Number of Inner Constraints", num2str(7 * ic))] + prior_rows + [
                 ("\\line", ""),
-                ("Total Number of Observations", num2str(n + 7 * ic)),
+                ("Total Number of Observations", num2str(n + 7 * ic + n_prior)),
                 ("\\n", ""),
-                ("Total Degrees of Freedom", num2str(n + 7 * ic - len(xhat))),
+                ("Total Degrees of Freedom", num2str(n + 7 * ic + n_prior - len(xhat))),
                 ("\\n", ""),
                 ("A-Posteriori", num2str(res.sigma02, 10)),
                 ("RMSx", num2str(res.rms[0], 10)),
@@ -350,6 +353,40 @@ def write_wgt(path, data, res):
             flag = "*" if min(w[i, 0], w[i, 1]) < WGT_FLAG else ""
             fh.write("\t".join([str(i + 1), data.pho_target[i], data.pho_image[i], _cell(w[i, 0]), _cell(w[i, 1]), flag])
                      + "\n")
+
+
+def write_prr(path, data, res):
+    """The prior-observation table <Output_Filename stem>.prr (no reference counterpart), written when priors
+    were used; tab-delimited in write_rsd's style: unknown name, prior value, std, adjusted value, v = adjusted -
+    prior, redundancy number r, test statistic w, flag per prior, in the order they were given.  Angles (w_, p_,
+    k_ unknowns) in degrees like the .pri table; r and w empty when the adjustment carries no covariance; flag is
+    * where |w| > W_CRITICAL."""
+    if getattr(res, "prior_index", None) is None:
+        raise ValueError("write_prr: the adjustment carries no priors (adjust(..., priors=))")
+    with open(path, "w") as fh:
+        for j, i in enumerate(res.prior_index):
+            name = res.xhatnames[i]
+            f = 180.0 / math.pi if name.split("_", 1)[0] in ("w", "p", "k") else 1.0
+            r = None if res.prior_r is None else res.prior_r[j]
+            w = None if res.prior_w is None else res.prior_w[j]
+            flag = "*" if w is not None and abs(w) > W_CRITICAL else ""
+            fh.write("\t".join([name] + [_cell(v) for v in (res.prior_value[j] * f, res.prior_sigma[j] * f, res.xhat[i] * f,
+                                                           res.prior_v[j] * f, r, w)] + [flag]) + "\n")
+
+
+def read_prr(path):
+    """write_prr's table back: (names, values (n, 6): prior, std, adjusted, v, r, w -- NaN for an empty cell --,
+    flagged (n) bool)"""
+    names, vals, flag = [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if len(c) != 8:
+                raise ValueError(f"read_prr: {path}: expected 8 tab-separated columns, got {len(c)}")
+            names.append(c[0])
+            vals.append([float(x) if x else math.nan for x in c[1:7]])
+            flag.append(c[7] == "*")
+    return names, np.array(vals, dtype=np.float64).reshape(-1, 6), np.array(flag, dtype=bool)
 
 
 def read_wgt(path):

@@ -135,6 +135,42 @@ int fba_image_order(const fba_problem* p, int32_t* order /*[n_slots]*/, int32_t*
 int fba_create(const fba_problem* p, const fba_settings* s, const fba_options* o, fba_ctx** out);
 void fba_destroy(fba_ctx* ctx);
 
+/* Prior observations of unknowns (no reference counterpart: the reference's unknowns are free, or fixed by
+ * switching an Estimate_* flag off or listing a control point): GNSS/INS-observed exterior orientation,
+ * ground control with a stated accuracy, interior orientation / distortion values of a calibration
+ * certificate.  Prior j observes unknown index[j] of the reference-layout xhat (0-based) with the value
+ * value[j] and the standard deviation sigma[j], in the units of xhat (radians for angles, the natural,
+ * de-scaled units for distortion terms); the priors are uncorrelated.  Each adds one unit row to the
+ * Gauss-Markov model: the row e_index[j], misclosure w_j = xhat[index[j]] - value[j] (computed minus
+ * observed, the reference's sign), weight p_j = 1 / sigma[j]^2.  The normal equations carry the distortion
+ * unknowns in scaled units (BuildAwG.m:419-451), so the row's entry for a K_j or P unknown is
+ * 1 / dist_scaling.  Robust loss and user weights act on image measurements only. */
+typedef struct fba_priors {
+    int64_t n;             /* number of priors                                               */
+    const int64_t* index;  /* [n] index into the reference-layout xhat, each at most once    */
+    const double* value;   /* [n] observed value l_j                                         */
+    const double* sigma;   /* [n] standard deviation, finite and > 0                         */
+} fba_priors;
+
+/* fba_create with priors; pr == NULL or pr->n == 0 is fba_create itself.  The priors are constants of the
+ * context: a tie point that carries one is accumulated by the general-point kernels instead of the chunked
+ * fast path, and that plan is laid out here.  Checked on the host before any GPU call (FBA_ERR_ARG, with
+ * a message): an index outside [0, u), an index given twice, a non-finite value, a sigma that is not
+ * finite or not > 0.  With world > 1 every rank passes the full list; rank 0 adds the priors of image and
+ * camera unknowns, a tie point's owner adds that point's, so the summed reduce buffer holds each once.
+ * Together with fba_options.split = 1 priors are refused (FBA_ERR_UNSUPPORTED). */
+int fba_create_priors(const fba_problem* p, const fba_settings* s, const fba_options* o, const fba_priors* pr,
+                      fba_ctx** out);
+
+/* The priors' residuals v_j = xhat[index[j]] - value[j] at the device xhat (the row is linear, so this
+ * is the reference's v = A delta + w convention exactly) and v'Pv's prior term.  *n (may be NULL)
+ * receives the number of priors; resid [n] (may be NULL): with world > 1, 0 for the priors this rank
+ * does not add; vtpv (may be NULL): this rank's sum of p_j v_j^2, added in a fixed order.
+ * fba_covariance and fba_reliability carry the priors through the normal equations; a prior's own
+ * redundancy number is r_j = 1 - cx_diag[index[j]] / (sigma02 sigma[j]^2) and its test statistic
+ * w_j = v_j / (sigma[j] sqrt(r_j)) (0 where r_j < 1e-10), host arithmetic on cx_diag. */
+int fba_get_priors(fba_ctx* ctx, int64_t* n, double* resid /*[n]*/, double* vtpv);
+
 /* The solve the context actually runs: *split = 1 when fba_options.split was honoured (subtree split:
  * reduce-buffer layout, ownership and the one-solve-per-accumulation rule of the split), 0 for the
  * replicated / single-GPU solve -- a split request falls back to the replicated solve when the block
@@ -194,7 +230,11 @@ int fba_adjust(fba_ctx* ctx, int32_t* iterations, double* deltasum_hist);
  * v [2*n_pts] (PHO order), rsd [5*n_pts] row-major per point: r, vx, vy, vr, vt,
  * stats [6]: RMSx, RMSy, RMS, sigma02, vTPv, n-u.  Pointers may be NULL.  With world > 1 each rank
  * fills only its observations (others 0) and stats hold this rank's partial sums
- * (sum vx^2, sum vy^2, 0, 0, vTPv, n-u); fba_finish_stats turns reduced sums into RMS / sigma02. */
+ * (sum vx^2, sum vy^2, 0, 0, vTPv, n-u); fba_finish_stats turns reduced sums into RMS / sigma02.
+ * With priors (fba_create_priors) stats[4] includes their term sum p_j v_j^2 (this rank's, with world > 1)
+ * and stats[5] is n + n_prior - u, so stats[3] follows with world 1; v, rsd and the RMS values are the
+ * image measurements' alone.  fba_finish_stats knows no priors: a multi-rank caller divides the reduced
+ * vTPv by stats[5] itself. */
 int fba_residuals(fba_ctx* ctx, double* v, double* rsd, double* stats);
 
 /* BuildRSD.m:1 for a caller-given v (e.g. the reference's v = A*delta + w, main.m:569-571): per PHO
