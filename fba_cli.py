@@ -10,6 +10,10 @@
     ... --priors                               (either command) the folder's .pri table, rows `<unknown name>
                                                <value> <std>`, as prior observations of unknowns; also writes
                                                the .prr table (report.write_prr)
+    ... --lm[=lambda0]                         (either command) Levenberg-Marquardt trials with step control, then
+                                               undamped passes, in place of the Gauss-Newton loop (first lambda
+                                               1e-3): for coarse starting values; also writes the .lm table
+                                               (report.write_lm)
 """
 import sys
 

@@ -47,17 +47,18 @@ def find_folders(folder, exts=EXTS, log=print):
     return out
 
 
-def batch_run(paths, device=0, robust=None, robust_k=None, priors=False):
+def batch_run(paths, device=0, robust=None, robust_k=None, priors=False, lm=None):
     """BatchRun.m:42-66: every data folder under the selected paths through main(folder, false);
     stops at the first folder whose main() fails.  Returns the list of (folder, main_error).
-    robust / robust_k: the robust loss of bundle.adjust, for every folder; priors: every folder's .pri table."""
+    robust / robust_k: the robust loss of bundle.adjust, for every folder; priors: every folder's .pri table;
+    lm: parse_lm's value, the damped loop (method="lm") for every folder."""
     from .bundle import main
     folders = []
     for p in paths:
         folders.extend(find_folders(p))
     done = []
     for f in folders:
-        err = main(f, False, device=device, **_robust_kw(robust, robust_k), **_priors_kw(priors))
+        err = main(f, False, device=device, **_robust_kw(robust, robust_k), **_priors_kw(priors), **_lm_kw(lm))
         done.append((f, err))
         if err == 1:
             break
@@ -72,6 +73,31 @@ def _robust_kw(robust, robust_k):
 def _priors_kw(priors):
     """main()'s keyword for the .pri table; none without it, so the call is the one it was"""
     return {"priors": True} if priors else {}
+
+
+def _lm_kw(lm):
+    """main()'s keywords for the damped loop (lm: None, True or lambda0); none without it, so the call is the one
+    it was"""
+    if lm is None or lm is False:
+        return {}
+    return {"method": "lm", "lm_options": None if lm is True else {"lambda0": float(lm)}}
+
+
+def parse_lm(args):
+    """--lm or --lm=lambda0 anywhere in args -> (args without it, None / True / lambda0): Levenberg-Marquardt
+    trials with step control in place of the Gauss-Newton loop.  ValueError for a lambda0 that is not a positive
+    number."""
+    rest, lm = [], None
+    for a in args:
+        if a == "--lm":
+            lm = True
+        elif a.startswith("--lm="):
+            lm = float(a.split("=", 1)[1])
+            if not (lm > 0.0 and lm < float("inf")):
+                raise ValueError("--lm: lambda0 must be a positive number")
+        else:
+            rest.append(a)
+    return rest, lm
 
 
 def parse_priors(args):
@@ -109,17 +135,19 @@ def parse_robust(args):
 
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
-    anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors')"""
-    args = parse_priors(parse_robust(args)[0])[0]
+    anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors', --lm parse_lm's)"""
+    args = parse_lm(parse_priors(parse_robust(args)[0])[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--robust LOSS[:k]] [--priors] | batch <folder>... "
-         "[--robust LOSS[:k]] [--priors]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
+         "batch <folder>... [--robust LOSS[:k]] [--priors] [--lm[=lambda0]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
          "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
          "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
-         "<std> per row) as prior observations of unknowns;\n      writes the .prr table")
+         "<std> per row) as prior observations of unknowns;\n      writes the .prr table\n  --lm[=lambda0]  "
+         "Levenberg-Marquardt trials with step control (first lambda 1e-3), then undamped passes, in place of\n"
+         "      the Gauss-Newton loop: for coarse starting values; writes the .lm table")
 
 
 def cli(argv=None):
@@ -128,6 +156,7 @@ def cli(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     try:
         argv, priors = parse_priors(argv)
+        argv, lm = parse_lm(argv)
         argv, robust, robust_k = parse_robust(argv)
     except ValueError as e:
         print(f"Error: {e}")
@@ -136,9 +165,10 @@ def cli(argv=None):
     if len(argv) >= 2 and argv[0] == "main":
         from .bundle import main
         folder, plot, reliability = parse_main(argv[1:])
-        return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors))
+        return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors),
+                    **_lm_kw(lm))
     if len(argv) >= 2 and argv[0] == "batch":
-        done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors))
+        done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors), **({"lm": lm} if lm else {}))
         return 1 if any(e for _, e in done) else 0
     print(USAGE)
     return 2

@@ -90,6 +90,8 @@ class Adjustment:
     prior_v: np.ndarray = None
     prior_r: np.ndarray = None
     prior_w: np.ndarray = None
+    # method="lm": one row per trial and polish pass of fba_adjust_lm -- lambda, cost after it, deltasum, accepted
+    lm_history: np.ndarray = None
 
 
 def _priors_of(data, priors):
@@ -115,7 +117,7 @@ def prior_statistics(sigma02, cx_diag, index, sigma, v):
 
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
-           reliability=False, priors=None) -> Adjustment:
+           reliability=False, priors=None, method="gn", lm_options=None) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -131,14 +133,27 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     priors (no reference counterpart): None, True (the folder's .pri table, data.priors) or (index, value, sigma)
     -- prior observations of unknowns, index into xhat, value and standard deviation in xhat's units
     (fba_create_priors).  sigma0^2 then counts them (v'Pv and the degrees of freedom), and Adjustment.prior_*
-    carry their residuals, redundancy numbers and test statistics."""
+    carry their residuals, redundancy numbers and test statistics.
+
+    method (no reference counterpart): "gn" is the reference's loop; "lm" replaces the L2 loop by fba_adjust_lm --
+    Levenberg-Marquardt trials with step control from the starting values, then undamped passes to the reference's
+    stopping rule -- for coarse starting values; lm_options: a capi.LMOptions or a dict of its fields.  iterations
+    and deltasum then count every trial and polish pass, Adjustment.lm_history holds the loop's table, and robust=
+    continues from there as it does after the Gauss-Newton loop."""
+    if method not in ("gn", "lm"):
+        raise ValueError(f"adjust: unknown method {method!r} (\"gn\" or \"lm\")")
     t0 = time.perf_counter()
     pri = _priors_of(data, priors)
     ctx = capi.Context(data.pack(), capi.make_settings(data.settings), device=device, verbose=verbose, priors=pri)
     try:
         if weights is not None:
             ctx.set_weights(weights)
-        it, hist = ctx.adjust()
+        lmh = None
+        if method == "lm":
+            nt, npol, lmh = ctx.adjust_lm(lm_options)
+            it, hist = nt + npol, lmh[:, 2].copy()
+        else:
+            it, hist = ctx.adjust()
         if robust:
             ctx.set_loss(robust, robust_k)
             cap, thr = max(int(ctx.settings.iteration_cap), 1), float(ctx.settings.threshold)
@@ -166,7 +181,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff, **pkw)
+                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -184,23 +199,27 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_wgt(os.path.join(folder, name + ".wgt"), data, res)
     if res.prior_index is not None:
         report.write_prr(os.path.join(folder, name + ".prr"), data, res)
+    if res.lm_history is not None:
+        report.write_lm(os.path.join(folder, name + ".lm"), res.lm_history)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False) -> int:
+         priors=False, method="gn", lm_options=None) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
     adjust()'s robust loss; the .wgt table (report.write_wgt) is written too.  priors=True: the folder's .pri
     table as prior observations of unknowns (io.read_pri; without the file main returns 1); the .prr table
-    (report.write_prr) is written too."""
+    (report.write_prr) is written too.  method="lm" (lm_options: adjust()'s): the damped loop of fba_adjust_lm
+    in place of the Gauss-Newton loop; the .lm table (report.write_lm) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
         data = load_folder(folder, project_dir=None if folder == project_dir else project_dir)
         res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k,
-                     **({"priors": True} if priors else {}))
+                     **({"priors": True} if priors else {}),
+                     **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:
         print(f"Error: {e}")

@@ -29,6 +29,7 @@ EXPORTS = (
     "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability",
     "fba_set_weights", "fba_set_loss", "fba_get_weights", "fba_last_timings", "fba_set_timing", "fba_set_probe",
     "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
+    "fba_set_damping", "fba_cost", "fba_adjust_lm",
 )
 
 
@@ -59,6 +60,14 @@ class Options(C.Structure):
 
 class Priors(C.Structure):
     _fields_ = [("n", C.c_int64), ("index", C.c_void_p), ("value", C.c_void_p), ("sigma", C.c_void_p)]
+
+
+class LMOptions(C.Structure):
+    """fba_lm_options; the defaults are the library's (a NULL pointer)"""
+    _fields_ = [(n, C.c_double) for n in ("lambda0", "up", "down", "lambda_min", "lambda_max", "ftol")]
+
+    def __init__(self, lambda0=1e-3, up=10.0, down=10.0, lambda_min=1e-12, lambda_max=1e8, ftol=1e-9):
+        super().__init__(lambda0, up, down, lambda_min, lambda_max, ftol)
 
 
 def pack_priors(priors):
@@ -121,6 +130,9 @@ def _load():
         "fba_probe_stats": ([P, P], C.c_int),
         "fba_set_spin_bound": ([P, C.c_int64], C.c_int),
         "fba_test_border_solve": ([I, P, P], C.c_int),
+        "fba_set_damping": ([P, D], C.c_int),
+        "fba_cost": ([P, P], C.c_int),
+        "fba_adjust_lm": ([P, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -287,6 +299,28 @@ class Context:
         it = C.c_int32()
         check(lib.fba_adjust(self.h, C.byref(it), ptr(hist)))
         return it.value, hist[: it.value].copy()
+
+    def set_damping(self, lam=0.0):
+        """fba_set_damping: Levenberg-Marquardt parameter of every following solve; 0 is Gauss-Newton"""
+        check(lib.fba_set_damping(self.h, float(lam)))
+
+    def cost(self):
+        """fba_cost: (total, image part, prior part) of the objective at the device xhat"""
+        out = np.zeros(3)
+        check(lib.fba_cost(self.h, ptr(out)))
+        return out
+
+    def adjust_lm(self, options=None):
+        """fba_adjust_lm: (trials, polish passes, history) -- history has one row per trial and pass:
+        lambda, cost after it, deltasum, accepted.  options: an LMOptions, a dict of its fields, or None."""
+        if isinstance(options, dict):
+            options = LMOptions(**options)
+        cap = max(int(self.settings.iteration_cap), 1)
+        hist = np.full((cap, 4), np.nan)
+        nt, npol = C.c_int32(), C.c_int32()
+        check(lib.fba_adjust_lm(self.h, None if options is None else C.byref(options), C.byref(nt), C.byref(npol),
+                                ptr(hist)))
+        return nt.value, npol.value, hist[: nt.value + npol.value].copy()
 
     def residuals(self):
         n = self.packed.n_pts

@@ -1023,7 +1023,7 @@ static int accumulate_body(Ctx* c) {
     if ((rc = launch_params(*c, nullptr, c->d_xlin))) return rc;
     mark(c, 1);
     // general tie points: their Jacobian rows, point tables and partials (ahead of the reductions)
-    if ((rc = launch_gen_tables(*c, nullptr)) || (rc = launch_gen_keys(*c))) return rc;
+    if ((rc = launch_gen_tables(*c, nullptr, c->damp_on())) || (rc = launch_gen_keys(*c))) return rc;
     mark(c, 2);
     // the camera-side priors behind the reductions' stores of the summed partials, ahead of the pack and the border
     if ((rc = launch_accumulate(*c)) || (rc = launch_gen_reduce(*c)) || (rc = launch_prior_cam(*c))) return rc;
@@ -1078,7 +1078,8 @@ static int solve_body(Ctx* c) {
         if ((rc = launch_cholesky(*c, 1))) return rc;
     } else {
         if (c->opt.world > 1 && (rc = launch_pack(*c, 1))) return rc;
-        if ((rc = launch_border(*c))) return rc;
+        // damping: S' + lambda diag(S') on the summed system, ahead of the border (its weights read the diagonal)
+        if ((rc = launch_damp_diag(*c)) || (rc = launch_border(*c))) return rc;
         mark(c, 4);
         if ((rc = launch_cholesky(*c))) return rc;
     }
@@ -1292,7 +1293,7 @@ static int solve_finish(Ctx* c, double* dsum, bool recopy) {
         return FBA_ERR_HIP;
     }
     c->have_delta = true;
-    c->have_factor = true;
+    c->have_factor = !c->damp_on();  // a damped solve's factor is not that of N: no covariance from it
     if (info != 0.0) {
         char buf[160];
         snprintf(buf, sizeof buf, "reduced normal matrix not positive definite (pivot %ld): singular / unconstrained network",
@@ -1716,6 +1717,138 @@ int fba_get_weights(fba_ctx* ctx, double* weight) {
     if ((rc = launch_get_weights(*c, d_w))) return rc;
     if (n > 0) FBA_HIP(hipMemcpyAsync(weight, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
     FBA_HIP(hipStreamSynchronize(c->stream));
+    return FBA_OK;
+}
+
+// ---- Levenberg-Marquardt damping, the cost and the damped loop (no reference counterpart) ----
+int fba_set_damping(fba_ctx* ctx, double lambda) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_set_damping: NULL context"); return FBA_ERR_ARG; }
+    if (!std::isfinite(lambda) || lambda < 0.0) { set_error("fba_set_damping: lambda must be finite and >= 0"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_set_damping between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    if (lambda > 0.0 && c->sched.split) {
+        set_error("fba_set_damping: not implemented for the subtree split (fba_solve_mode 1); use the replicated solve");
+        return FBA_ERR_UNSUPPORTED;
+    }
+    if (lambda == c->damping) return FBA_OK;
+    int rc;
+    if ((lambda > 0.0) != c->damp_on()) {
+        // on / off: other kernels and launches in both halves (the WH instantiations, k_damp_diag, the border
+        // weights' own launch), so both captured graphs go; lambda itself is a device scalar, and a change of
+        // its value re-captures nothing
+        if ((rc = weighting_changed(c))) return rc;
+        if (c->graph[1]) {
+            (void)hipGraphExecDestroy(c->graph[1]);
+            c->graph[1] = nullptr;
+        }
+    } else {
+        // lambda1 -> lambda2: the tie points of a held linearisation were eliminated with V + lambda1 diag(V), and
+        // k_damp_diag would scale S' with lambda2 -- a system of neither; fba_solve_update asks for a new fba_accumulate
+        FBA_HIP(hipStreamSynchronize(c->stream));
+        c->have_lin = false;
+    }
+    FBA_HIP(hipMemcpy(c->d_scal + SCAL_DAMP, &lambda, sizeof lambda, hipMemcpyHostToDevice));
+    c->damping = lambda;
+    c->have_factor = false;
+    return FBA_OK;
+}
+
+int fba_cost(fba_ctx* ctx, double* cost) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !cost) { set_error("fba_cost: NULL argument"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_cost between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const size_t nblk = (size_t)((c->n_obs + 255) / 256);
+    double* d_w = nullptr;
+    int rc;
+    if ((rc = ws_get(*c, 73, sizeof(double) * (nblk + 4), (void**)&d_w)) || (rc = launch_cost(*c, d_w + 4, d_w))) return rc;
+    FBA_HIP(hipMemcpyAsync(cost, d_w, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    return FBA_OK;
+}
+
+int fba_adjust_lm(fba_ctx* ctx, const fba_lm_options* o, int32_t* trials, int32_t* polish, double* hist) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_adjust_lm: NULL context"); return FBA_ERR_ARG; }
+    if (c->opt.world != 1) { set_error("fba_adjust_lm is single-GPU (world == 1)"); return FBA_ERR_UNSUPPORTED; }
+    const fba_lm_options def{1e-3, 10.0, 10.0, 1e-12, 1e8, 1e-9};
+    const fba_lm_options q = o ? *o : def;
+    if (!(q.lambda0 > 0.0) || !(q.up > 1.0) || !(q.down > 1.0) || !(q.lambda_min > 0.0) || !(q.lambda_max >= q.lambda0) ||
+        !(q.ftol >= 0.0) || !std::isfinite(q.lambda_max) || !std::isfinite(q.up) || !std::isfinite(q.down)) {
+        set_error("fba_adjust_lm: options need lambda0 > 0, up > 1, down > 1, lambda_min > 0, lambda0 <= lambda_max < inf, ftol >= 0");
+        return FBA_ERR_ARG;
+    }
+    if (trials) *trials = 0;
+    if (polish) *polish = 0;
+    const int cap = std::max(c->set.iteration_cap, 1);
+    const size_t xbytes = sizeof(double) * (size_t)c->L.u_full;
+    double* d_save = nullptr;
+    int rc, n = 0, nt = 0;
+    if ((rc = ws_get(*c, 74, std::max<size_t>(xbytes, 8), (void**)&d_save))) return rc;
+    auto record = [&](double lambda, double cost, double dsum, int acc) {
+        if (hist) { hist[4 * n] = lambda; hist[4 * n + 1] = cost; hist[4 * n + 2] = dsum; hist[4 * n + 3] = acc; }
+        ++n;
+    };
+    auto restore = [&]() -> int {  // xhat as before the trial; its linearisation and correction are not this xhat's
+        FBA_HIP(hipMemcpyAsync(c->d_xfull, d_save, xbytes, hipMemcpyDeviceToDevice, c->stream));
+        c->have_lin = false;
+        c->have_delta = false;
+        return FBA_OK;
+    };
+    // every exit leaves the context undamped: the damped phase's failures through fail(), the not-converged exit by
+    // its own call, and the polish phase runs with damping already 0.  fba_set_damping(0) cannot fail here except on a
+    // HIP error, which the failure being returned already reports, so its result is dropped
+    auto fail = [&](int code) { (void)fba_set_damping(ctx, 0.0); return code; };  // (keeps the failure's message)
+    double f3[3], F, lambda = q.lambda0;
+    if ((rc = fba_cost(ctx, f3))) return rc;
+    F = f3[0];
+    // damped phase: at most cap - 1 trials, so that one polish pass always fits under Iteration_Cap
+    while (n < cap - 1) {
+        FBA_HIP(hipMemcpyAsync(d_save, c->d_xfull, xbytes, hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = fba_set_damping(ctx, lambda))) return fail(rc);
+        double dsum = 0.0, Fn = HUGE_VAL;
+        rc = fba_step(ctx, &dsum);
+        if (rc != FBA_OK && rc != FBA_ERR_NOT_SPD) return fail(rc);
+        if (rc == FBA_OK) {
+            if ((rc = fba_cost(ctx, f3))) return fail(rc);
+            Fn = f3[0];
+        }
+        ++nt;
+        if (trials) *trials = nt;
+        if (std::isfinite(Fn) && std::fabs(Fn - F) <= q.ftol * F) {  // the differences have reached rounding: stop here
+            const int keep = Fn <= F;
+            if (!keep && (rc = restore())) return fail(rc);
+            record(lambda, Fn, dsum, keep);
+            if (keep) F = Fn;
+            break;
+        }
+        if (std::isfinite(Fn) && Fn < F) {
+            record(lambda, Fn, dsum, 1);
+            F = Fn;
+            lambda = std::max(lambda / q.down, q.lambda_min);
+            if (dsum <= c->set.threshold) break;
+            continue;
+        }
+        if ((rc = restore())) return fail(rc);
+        record(lambda, Fn, dsum, 0);
+        lambda *= q.up;
+        if (lambda > q.lambda_max) {
+            (void)fba_set_damping(ctx, 0.0);
+            set_error("fba_adjust_lm: not converged, no damped step lowers the cost up to lambda_max");
+            return FBA_ERR_NONFINITE;
+        }
+    }
+    // polish: plain Gauss-Newton passes to the reference's stop rule (main.m:412, :490-493), at least one, so
+    // that v, sigma02, Cx and the reliability numbers come from an undamped last pass as after fba_adjust
+    if ((rc = fba_set_damping(ctx, 0.0))) return rc;
+    double dsum = 100.0;
+    int np = 0;
+    while (dsum > c->set.threshold && n < cap) {
+        if ((rc = fba_step(ctx, &dsum))) return rc;
+        if ((rc = fba_cost(ctx, f3))) return rc;
+        record(0.0, f3[0], dsum, 1);
+        ++np;
+        if (polish) *polish = np;
+    }
     return FBA_OK;
 }
 

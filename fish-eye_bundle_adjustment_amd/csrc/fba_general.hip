@@ -57,13 +57,16 @@ __device__ __forceinline__ void tri_ab(int q, int& a, int& b) {
 // PR: the points' prior observations (fba_create_priors): unit rows on the point's own coordinates, so V_dd += p_d
 // and b_d += p_d (X_d - l_d) after the wave sums, from prior [n_gp][6] (p0 p1 p2 l0 l1 l2, p = 0: none) and the
 // point's coordinates at the linearisation point x; everything downstream reads V^-1, R, rb, vb from the table.
-// Without priors the PR = false instantiation runs: the kernel as it was
-template <int NK, bool PR>
+// Without priors the PR = false instantiation runs: the kernel as it was.
+// DP: Levenberg-Marquardt damping (fba_set_damping), V + lambda diag(V) after the prior terms and before V is
+// factored or inverted, lambda = *damp (the context's scalar); the DP = false instantiations are the kernel as it was
+template <int NK, bool PR, bool DP>
 __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, const int32_t* __restrict__ A,
                                                   const GenPlan g, double* __restrict__ gpt, double* __restrict__ gcu,
                                                   double* __restrict__ gug, double px, double py,
                                                   const double* __restrict__ prior, const double* __restrict__ x,
-                                                  const int32_t* __restrict__ lp_tie, int64_t u_c) {
+                                                  const int32_t* __restrict__ lp_tie, int64_t u_c,
+                                                  const double* __restrict__ damp) {
     using Q = GL<NK>;
     constexpr int CW = Q::CW, NJ = Q::NJ, JS = Q::JS, GC = Q::GC;
     const int q = blockIdx.x, l = threadIdx.x;
@@ -89,6 +92,10 @@ __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, 
         const double* X = x + u_c + 3 * (int64_t)lp_tie[g.lp0 + q];
         V[0] += pr[0]; V[3] += pr[1]; V[5] += pr[2];
         V[6] += pr[0] * (X[0] - pr[3]); V[7] += pr[1] * (X[1] - pr[4]); V[8] += pr[2] * (X[2] - pr[5]);
+    }
+    if constexpr (DP) {
+        const double f = 1.0 + *damp;
+        V[0] *= f; V[3] *= f; V[5] *= f;
     }
     const double V00 = V[0], V01 = V[1], V02 = V[2], V11 = V[3], V12 = V[4], V22 = V[5];
     const double b0 = V[6], b1 = V[7], b2 = V[8];
@@ -424,19 +431,23 @@ __global__ __launch_bounds__(256) void k_cov_gen(const double* __restrict__ S, i
 
 static inline unsigned grid_of(int64_t n, int per) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
 
-int launch_gen_tables(Ctx& c, const double* x) {
+int launch_gen_tables(Ctx& c, const double* x, bool damp) {
     const GenPlan& g = c.gen;
     if (g.n_gp == 0) return FBA_OK;
     int rc;
     if ((rc = launch_linearize_range(c, x, c.n_chunks_lr, c.n_chunks))) return rc;  // J of the general observations
     const double px = 1.0 / (c.set.meas_std_x * c.set.meas_std_x), py = 1.0 / (c.set.meas_std_y * c.set.meas_std_y);
     const double* xp = x ? x : c.d_xfull;
-#define GP_ARGS c.d_J, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, px, py, c.d_gprior, xp, c.d_lp_tie, c.L.u_c
-#define GP(NKV)                                                                 \
-    if (c.d_gprior)                                                             \
-        k_gen_point<NKV, true><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS); \
-    else                                                                        \
-        k_gen_point<NKV, false><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS)
+#define GP_ARGS c.d_J, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, px, py, c.d_gprior, xp, c.d_lp_tie, c.L.u_c, c.d_scal + SCAL_DAMP
+#define GP(NKV)                                                                        \
+    if (c.d_gprior && damp)                                                            \
+        k_gen_point<NKV, true, true><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS);  \
+    else if (damp)                                                                     \
+        k_gen_point<NKV, false, true><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS); \
+    else if (c.d_gprior)                                                               \
+        k_gen_point<NKV, true, false><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS); \
+    else                                                                               \
+        k_gen_point<NKV, false, false><<<(unsigned)g.n_gp, 64, 0, c.stream>>>(GP_ARGS)
     GEN_NK_DISPATCH(c.L.nk, GP);
 #undef GP_ARGS
 #undef GP

@@ -31,6 +31,7 @@ constexpr int SCAL_SPINS = 6;  // d_scal slot: this context's hand-off poll boun
 inline double spin_bound_value(long long spins) {
     return spins <= 0 ? (double)(1u << 22) : (double)(spins < 0xffffffffLL ? spins : 0xffffffffLL);
 }
+constexpr int SCAL_DAMP = 7;   // d_scal slot: the Levenberg-Marquardt damping parameter lambda (fba_set_damping; 0: off)
 constexpr int CHUNK_OBS = 256;  // observations per k_lin_reduce / k_lin_point workgroup (chunk)
 // tie points per chunk and co-visibility terms per chunk staged in LDS (a single larger point's are
 // read from HBM instead): smaller for nK >= 6, whose wider Jacobian rows leave less of the 160 KiB LDS
@@ -339,6 +340,9 @@ struct Ctx {
     double loss_k = 0.0;
     bool whiten_on() const { return weights_on || loss != 0; }
     Whiten whiten() const { return Whiten{weights_on ? d_sw : nullptr, loss, loss_k}; }
+    // Levenberg-Marquardt damping (fba_set_damping): lambda, also in d_scal[SCAL_DAMP] for the kernels
+    double damping = 0.0;
+    bool damp_on() const { return damping > 0.0; }
     // prior observations of unknowns (fba_create_priors; constants of the context).  A prior is ADDED by one
     // rank: image / camera unknowns by rank 0, a tie point's by its owner
     int64_t n_prior = 0;             // all priors of the call
@@ -416,7 +420,7 @@ int launch_linearize_range(Ctx& c, const double* x, int64_t c0, int64_t c1, bool
 // general tie points (fba_general.hip): Jacobian rows of their observations + point tables
 // (gen_tables), their partials (gen_keys), the blocks only they touch (gen_reduce, after
 // launch_accumulate), back-substitution (gen_backsub), tie variances (gen_cov, fba_cov.hip)
-int launch_gen_tables(Ctx& c, const double* x);
+int launch_gen_tables(Ctx& c, const double* x, bool damp = false);  // damp: V + lambda diag(V) (the accumulation's)
 int launch_gen_keys(Ctx& c);
 int launch_gen_reduce(Ctx& c);
 int launch_gen_backsub(Ctx& c);
@@ -424,6 +428,8 @@ int launch_gen_cov(Ctx& c, const double* Z, const double* Wz, int nz, double* pd
 int launch_accumulate(Ctx& c, bool zeroed = false);  // zero S (unless zeroed), image, pair, camera blocks
 int launch_prior_cam(Ctx& c);    // camera-side priors into S's diagonal and RHS row (after the reductions' stores)
 int launch_prior_resid(Ctx& c);  // prior residuals at d_xfull and their sum p v^2 -> d_pr_out
+int launch_damp_diag(Ctx& c);    // damping on: S' + lambda diag(S') on the estimated camera-side rows (solve half)
+int launch_cost(Ctx& c, double* d_part, double* d_out);  // cost at d_xfull -> d_out[3] (total, image, prior part)
 int launch_border(Ctx& c);       // alpha, G G^T border, RHS rows
 int chol_setup(Ctx& c);
 int acc_setup(Ctx& c);            // kernel attributes of the accumulation kernels          // one-time kernel attributes, streams, events

@@ -514,7 +514,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     double* __restrict__ ppart, double* __restrict__ ipart, double* __restrict__ cpart, int64_t u_c, int type,
     int cam_stride, unsigned eop_mask, unsigned cam_mask, double px, double py, uint64_t* __restrict__ tprof,
     int n_chunks, double* __restrict__ S, int64_t ld, const int32_t* __restrict__ zblk,
-    const int32_t* __restrict__ xoff, double* __restrict__ Ug, const Whiten wh) {
+    const int32_t* __restrict__ xoff, double* __restrict__ Ug, const Whiten wh, const double* __restrict__ damp) {
     using LY = Lay<NK>;
     using R_ = LR<NK>;
     if ((int)blockIdx.x >= n_chunks) {  // tail workgroups: zero one 128x128 block of the factor's pattern
@@ -676,6 +676,14 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
                 W1[q][m] = keep + dpp_d<0xB1>(give);
             }
         const int qb = (hA ? 2 * CWQ : 0) + (hB ? CWQ : 0);  // this lane's first camera column
+        // Levenberg-Marquardt damping (fba_set_damping): V + lambda diag(V), applied last, so V^-1, R and
+        // everything formed from them below are the damped point block's.  The WH = true instantiations
+        // carry it (launched with s = 1 when only damping is set); lambda is read here, at its only use,
+        // from the context's scalars (0 when damping is off: the factor 1 is exact)
+        if constexpr (WH) {
+            const double f = 1.0 + *damp;
+            V[0] *= f; V[3] *= f; V[5] *= f;
+        }
         const double V00 = V[0], V01 = V[1], V02 = V[2], V11 = V[3], V12 = V[4], V22 = V[5];
         const double b0 = V[6], b1 = V[7], b2 = V[8];
         // symmetric 3x3 inverse (adjugate)
@@ -1508,6 +1516,89 @@ int launch_prior_resid(Ctx& c) {
     return FBA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Levenberg-Marquardt damping of the camera side (fba_set_damping; no reference counterpart): the summed
+// reduced system S' = N_cc - N_cp V_lambda^-1 N_pc gets S' + lambda diag(S'), one read-multiply-write per
+// estimated image / camera row, in the solve half behind launch_pack / the all-reduce and ahead of the
+// border (whose weight sums read the damped diagonal).  Fixed parameters and padding slots are left alone:
+// k_border_rhs writes their unit rows.  lambda from scal[SCAL_DAMP]
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_damp_diag(double* __restrict__ S, int64_t ld, int64_t u_c,
+                                                   const uint8_t* __restrict__ active, const double* __restrict__ scal) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= u_c || !active[i]) return;
+    S[i * ld + i] *= 1.0 + scal[SCAL_DAMP];
+}
+
+int launch_damp_diag(Ctx& c) {
+    if (!c.damp_on() || c.L.u_c == 0) return FBA_OK;
+    k_damp_diag<<<(unsigned)((c.L.u_c + 255) / 256), 256, 0, c.stream>>>(c.d_S, c.L.ld, c.L.u_c, c.d_active, c.d_scal);
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// cost at the current parameters (fba_cost; no reference counterpart): F = sum rho(t^2) over this rank's
+// image points, t^2 = px (s0 w0)^2 + py (s1 w1)^2 from the forward model alone (obs_model's Jacobian is dead
+// code here), s = sqrt(user weight), rho the loss whose IRLS factor whiten_rows applies: t^2 | Huber
+// t^2 (t <= k), 2 k t - k^2 | Cauchy k^2 ln(1 + t^2 / k^2).  One thread per observation of any kind
+// (chunked, general, control), block partials by block_sum256, added in a fixed order by one workgroup
+// (k_sum_parts' pattern): no atomics, two calls are bitwise equal.
+// ------------------------------------------------------------------------------------------------
+template <int NK, bool WH>
+__global__ __launch_bounds__(256) void k_cost(const double* __restrict__ xy, const int32_t* __restrict__ img,
+                                              const int32_t* __restrict__ cam, const int32_t* __restrict__ pt,
+                                              const int32_t* __restrict__ lp_tie, const double* __restrict__ ctl,
+                                              const double* __restrict__ xfull, const double* __restrict__ img_tab,
+                                              const double* __restrict__ cam_tab, int64_t n_obs, int64_t u_c, int type,
+                                              int cam_stride, double px, double py, const Whiten wh,
+                                              double* __restrict__ part) {
+    __shared__ double red[4];
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double a = 0.0;
+    if (o < n_obs) {
+        const double2 xyv = *reinterpret_cast<const double2*>(xy + 2 * o);
+        const int p = pt[o];
+        const double* q = p >= 0 ? xfull + u_c + 3 * (int64_t)lp_tie[p] : ctl + 3 * (int64_t)(-1 - p);
+        double jr[2][Lay<NK>::NJ];
+        double w0, w1;
+        obs_model<NK>(xyv.x, xyv.y, img_tab + (int64_t)img[o] * IMG_TAB, cam_tab + (int64_t)cam[o] * cam_stride, q[0], q[1],
+                      q[2], p >= 0, type, 0u, 0u, jr, w0, w1);
+        if constexpr (WH) {
+            if (wh.sw) {
+                const double2 sv = *reinterpret_cast<const double2*>(wh.sw + 2 * o);
+                w0 *= sv.x;
+                w1 *= sv.y;
+            }
+        }
+        const double t2 = px * (w0 * w0) + py * (w1 * w1);
+        a = t2;
+        if constexpr (WH) {
+            const double k2 = wh.k * wh.k;
+            if (wh.loss == FBA_LOSS_HUBER) a = t2 <= k2 ? t2 : 2.0 * wh.k * sqrt(t2) - k2;
+            else if (wh.loss == FBA_LOSS_CAUCHY) a = k2 * log1p(t2 / k2);
+        }
+    }
+    const double s = block_sum256(a, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// out[1] = the image part (the block partials in k_sum_parts' order), out[2] = the prior part (k_prior_vtpv's
+// sum, or 0), out[0] = their sum
+__global__ __launch_bounds__(256) void k_cost_sum(const double* __restrict__ part, int n, const double* __restrict__ prior,
+                                                  double* __restrict__ out) {
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += part[i];  // thread t: parts t, t + 256, ... in order
+    const double sum = block_sum256(a, red);
+    if (threadIdx.x == 0) {
+        const double pv = prior ? *prior : 0.0;
+        out[0] = sum + pv;
+        out[1] = sum;
+        out[2] = pv;
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // residuals: v = J delta + w (main.m:569; delta = de-scaled last correction, as the reference),
@@ -1740,9 +1831,9 @@ __global__ __launch_bounds__(256) void k_zero_blocks(double* __restrict__ S, int
 
 // the border weights read the image rows' diagonal of S: final at the end of the accumulation when no
 // general tie points (launch_gen_reduce), no camera-side prior (launch_prior_cam) and no other rank
-// (launch_pack / the split) add to S after it
+// (launch_pack / the split) add to S after it, and damping (k_damp_diag, in the solve half) does not scale it
 bool border_weights_in_accumulate(const Ctx& c) {
-    return c.n_chunks_lr > 0 && c.gen.n_gp == 0 && c.n_pcam == 0 && c.opt.world <= 1 && !c.sched.split;
+    return c.n_chunks_lr > 0 && c.gen.n_gp == 0 && c.n_pcam == 0 && c.opt.world <= 1 && !c.sched.split && !c.damp_on();
 }
 
 int launch_accumulate(Ctx& c, bool zeroed) {
@@ -1759,11 +1850,11 @@ int launch_accumulate(Ctx& c, bool zeroed) {
     c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, c.d_xfull, c.d_img_tab, c.d_cam_tab, c.d_chunk_obs,    \
         c.d_chunk_pt, c.d_lp_start, c.d_acc, c.acc, c.d_WT, c.d_pt_tab, c.d_ppart, c.d_ipart, c.d_cpart, c.L.u_c, \
         c.set.type, c.cam_tab_stride, em, cm, px, py, c.d_lrprof, (int)nlr, c.d_S, L.ld, c.d_sched + c.sched.zero, \
-        c.d_xoff, c.d_U, c.whiten()
+        c.d_xoff, c.d_U, c.whiten(), c.d_scal + SCAL_DAMP
 #define ACC(NKV)                                                                                                  \
-    if (nlr > 0 && c.ik_lanes == 4 && !c.whiten_on())                                                             \
+    if (nlr > 0 && c.ik_lanes == 4 && !lr_wh)                                                                     \
         k_lin_reduce<NKV, 4, false><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);    \
-    else if (nlr > 0 && !c.whiten_on())                                                                           \
+    else if (nlr > 0 && !lr_wh)                                                                                   \
         k_lin_reduce<NKV, 8, false><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);    \
     else if (nlr > 0 && c.ik_lanes == 4)                                                                          \
         k_lin_reduce<NKV, 4, true><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);     \
@@ -1778,6 +1869,9 @@ int launch_accumulate(Ctx& c, bool zeroed) {
     k_red_cam<NKV><<<(unsigned)(L.n_cam + (bwa ? BW_SEG : 0)), 256, 0, c.stream>>>(c.d_cseg, c.d_S, L.ld, L.n_pad,   \
                                                                                L.n_img, L.n_cam, bw)
     const bool bwa = border_weights_in_accumulate(c);
+    // damping rides on the WH = true instantiations (s = 1 without weights or a loss): the undamped,
+    // unweighted default launches the WH = false kernels as before
+    const bool lr_wh = c.whiten_on() || c.damp_on();
     const BorderW bw{c.d_G, c.d_scal, c.d_bscr, c.n_loc, c.set.inner_constraints};
     FBA_NK_DISPATCH(L.nk, ACC);
 #undef ACC
@@ -1855,6 +1949,35 @@ int launch_residuals(Ctx& c) {
     FBA_NK_DISPATCH(L.nk, RS);
 #undef RS
 #undef RS_ARGS
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+// the cost at d_xfull into d_out[3] (total, image part, prior part); part: [ceil(n_obs / 256)] scratch.
+// Shared buffers it rewrites: the image / camera tables (launch_params) and, with priors, d_pr_out
+// (launch_prior_resid).  Both are functions of d_xfull alone, so between fba_accumulate and fba_solve_update -- xhat
+// unchanged -- they are rewritten with the values they already hold, and the solve half reads what it would have
+int launch_cost(Ctx& c, double* d_part, double* d_out) {
+    int rc;
+    if ((rc = launch_params(c))) return rc;  // the image / camera tables at d_xfull
+    const int nblk = (int)((c.n_obs + 255) / 256);
+    if (nblk > 0) {
+        const Whiten wh = c.whiten();
+#define CS_ARGS                                                                                                    \
+    c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, c.d_xfull, c.d_img_tab, c.d_cam_tab, c.n_obs, c.L.u_c,  \
+        c.set.type, c.cam_tab_stride, px_of(c), py_of(c), wh, d_part
+#define CS(NKV)                                                       \
+    if (c.whiten_on())                                                \
+        k_cost<NKV, true><<<nblk, 256, 0, c.stream>>>(CS_ARGS);       \
+    else                                                              \
+        k_cost<NKV, false><<<nblk, 256, 0, c.stream>>>(CS_ARGS)
+        FBA_NK_DISPATCH(c.L.nk, CS);
+#undef CS
+#undef CS_ARGS
+        FBA_HIP(hipGetLastError());
+    }
+    if (c.n_prior > 0 && (rc = launch_prior_resid(c))) return rc;
+    k_cost_sum<<<1, 256, 0, c.stream>>>(d_part, nblk, c.n_prior > 0 ? c.d_pr_out + c.n_prior : nullptr, d_out);
     FBA_HIP(hipGetLastError());
     return FBA_OK;
 }

@@ -374,6 +374,16 @@ def write_prr(path, data, res):
                                                            res.prior_v[j] * f, r, w)] + [flag]) + "\n")
 
 
+def write_lm(path, history):
+    """The damped loop's table <Output_Filename stem>.lm (no reference counterpart), written with method="lm";
+    tab-delimited in write_rsd's style, one row per trial and polish pass of fba_adjust_lm: number (1-based),
+    lambda (0 for an undamped polish pass), the cost after it, deltasum, accepted (1 / 0)."""
+    h = np.asarray(history, dtype=np.float64).reshape(-1, 4)
+    with open(path, "w") as fh:
+        for i, (lam, cost, dsum, acc) in enumerate(h):
+            fh.write("\t".join([str(i + 1), _cell(lam), _cell(cost), _cell(dsum), str(int(acc))]) + "\n")
+
+
 def read_prr(path):
     """write_prr's table back: (names, values (n, 6): prior, std, adjusted, v, r, w -- NaN for an empty cell --,
     flagged (n) bool)"""

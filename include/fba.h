@@ -306,6 +306,56 @@ int fba_set_weights(fba_ctx* ctx, const double* weight /*[2*n_pts], PHO order, x
 int fba_set_loss(fba_ctx* ctx, int32_t loss, double k);
 int fba_get_weights(fba_ctx* ctx, double* weight /*[2*n_pts]*/);
 
+/* Levenberg-Marquardt damping with step control (no reference counterpart: main.m:407-494 takes every
+ * Gauss-Newton step at full length, whatever it does to the cost).
+ *
+ * fba_set_damping: lambda = 0 (the default) is Gauss-Newton on the kernels and launches as they are without
+ *   this call; lambda > 0 damps every following solve of the context: it solves (N + lambda D) delta = -A'Pw,
+ *   with inner constraints the same bordered system with N + lambda D in place of N.  D is a positive
+ *   diagonal: for a tie point diag(V) of its block V = Jp'PJp (weights, loss factor and priors included), so the
+ *   point is eliminated with V_l = V + lambda diag(V); for the image and camera unknowns diag(S') of the reduced
+ *   system S' = N_cc - N_cp V_l^-1 N_pc formed with the damped V (camera-side priors and the ranks' sum
+ *   included), so the solve factors S' + lambda diag(S').  A valid Levenberg-Marquardt metric, but not
+ *   Marquardt's diag(N) on the camera rows.  A negative or non-finite lambda is FBA_ERR_ARG; lambda > 0 on a
+ *   subtree-split context (fba_solve_mode 1) is FBA_ERR_UNSUPPORTED.  Not between fba_solve_update_async and
+ *   fba_solve_finish.  Any change of lambda invalidates the last linearisation (the tie points were eliminated
+ *   with the earlier lambda): fba_solve_update then asks for a new fba_accumulate.  Switching damping on or off
+ *   also re-captures the graphs, like fba_set_weights; changing lambda between damped steps costs one scalar
+ *   copy and re-captures nothing.  After a damped solve the factor is not that of
+ *   N: fba_covariance and fba_reliability return FBA_ERR_ARG until an undamped solve; fba_residuals works.
+ * fba_cost: the objective at the device xhat, from the forward model alone (no linearisation is needed or
+ *   touched; xhat and every later step are bitwise as without the call):
+ *     F = sum over image points rho(t^2) + sum over priors p_j (xhat[index_j] - l_j)^2,
+ *     t^2 = px (s0 w0)^2 + py (s1 w1)^2,  w the misclosure, s = sqrt(user weight) (1 without),
+ *     rho(t^2) = t^2 (no loss) | Huber: t^2 (t <= k), 2 k t - k^2 | Cauchy: k^2 ln(1 + t^2 / k^2)
+ *   -- the losses whose IRLS factors fba_set_loss applies; without weights or loss F = w'Pw of BuildAwG's
+ *   misclosure.  cost[0] total, [1] image part, [2] prior part, each added in a fixed order (two calls are
+ *   bitwise equal).  With world > 1 this rank's share: its observations, and the priors it adds (fba_get_priors).
+ * fba_adjust_lm: the damped loop, then undamped passes, from the context's current xhat (world == 1 only,
+ *   FBA_ERR_UNSUPPORTED otherwise):
+ *     F = cost at x; lambda = lambda0
+ *     trial: save x (device copy); one step at lambda; Fn = cost at x + delta
+ *       |Fn - F| <= ftol F    -> keep the step if Fn <= F, else restore x; end the damped phase
+ *       Fn finite and Fn < F  -> accept; F = Fn; lambda = max(lambda / down, lambda_min);
+ *                                end the damped phase if deltasum <= Threshold_Value
+ *       otherwise             -> restore x; lambda = lambda up; lambda > lambda_max: FBA_ERR_NONFINITE
+ *                                (not converged; message set)
+ *       FBA_ERR_NOT_SPD from the trial's solve counts as "otherwise"; any other error returns
+ *     polish: damping off; plain Gauss-Newton steps while deltasum > Threshold_Value (at least one)
+ *   Iteration_Cap bounds trials + polish passes together, as main.m:490-493 bounds passes; the damped phase
+ *   takes at most Iteration_Cap - 1 of them.  The polish passes make v, sigma02, Cx and the reliability numbers
+ *   those of an undamped last pass, exactly as after fba_adjust.  The ftol rule ends the damped phase where
+ *   the cost differences fall to rounding and accept / reject would be noise.  *trials and *polish (may be
+ *   NULL) receive the two counts; hist (may be NULL, capacity 4 * Iteration_Cap) one row per trial and pass:
+ *   lambda, the cost after it, deltasum, accepted (1 / 0); polish rows carry lambda = 0 and accepted = 1. */
+typedef struct fba_lm_options {
+    double lambda0, up, down, lambda_min, lambda_max, ftol;
+} fba_lm_options; /* NULL: 1e-3, 10, 10, 1e-12, 1e8, 1e-9 */
+int fba_set_damping(fba_ctx* ctx, double lambda);
+int fba_cost(fba_ctx* ctx, double* cost /*[3]: total, image part, prior part*/);
+int fba_adjust_lm(fba_ctx* ctx, const fba_lm_options* o, int32_t* trials, int32_t* polish,
+                  double* hist /*[4*Iteration_Cap]: lambda, cost after, deltasum, accepted (1/0)*/);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
