@@ -92,6 +92,11 @@ class Adjustment:
     prior_w: np.ndarray = None
     # method="lm": one row per trial and polish pass of fba_adjust_lm -- lambda, cost after it, deltasum, accepted
     lm_history: np.ndarray = None
+    # point precision (point_precision=True), TIE order: every tie point's full 3 x 3 block of the final Cx, the
+    # 1-sigma semi-axes a >= b >= c of its error ellipsoid and the three unit axis vectors as rows
+    cx_tie: np.ndarray = None      # (n_tie, 3, 3), full symmetric
+    ell_axes: np.ndarray = None    # (n_tie, 3)
+    ell_dirs: np.ndarray = None    # (n_tie, 3, 3)
 
 
 def _priors_of(data, priors):
@@ -117,7 +122,7 @@ def prior_statistics(sigma02, cx_diag, index, sigma, v):
 
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
-           reliability=False, priors=None, method="gn", lm_options=None) -> Adjustment:
+           reliability=False, priors=None, method="gn", lm_options=None, point_precision=False) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -139,7 +144,12 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     Levenberg-Marquardt trials with step control from the starting values, then undamped passes to the reference's
     stopping rule -- for coarse starting values; lm_options: a capi.LMOptions or a dict of its fields.  iterations
     and deltasum then count every trial and polish pass, Adjustment.lm_history holds the loop's table, and robust=
-    continues from there as it does after the Gauss-Newton loop."""
+    continues from there as it does after the Gauss-Newton loop.
+
+    point_precision (no reference counterpart: main.m:460-482 keeps the diagonal of Cx): fba_postfit_outputs in
+    place of fba_covariance / fba_reliability -- the same outputs (reliability's too when that is asked for), plus
+    every tie point's full 3 x 3 covariance block and 1-sigma error ellipsoid: Adjustment.cx_tie, ell_axes,
+    ell_dirs."""
     if method not in ("gn", "lm"):
         raise ValueError(f"adjust: unknown method {method!r} (\"gn\" or \"lm\")")
     t0 = time.perf_counter()
@@ -167,7 +177,11 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         v, rsd, st = ctx.residuals()
         eff = ctx.get_weights() if (weights is not None or robust) else None
         red = wst = None
-        if reliability:
+        ppk = {}
+        if point_precision:
+            cxd, corr, red, wst, blk, ell = ctx.postfit(st[3], reliability=reliability)
+            ppk = dict(cx_tie=capi.tie_blocks(blk), ell_axes=ell[:, :3].copy(), ell_dirs=ell[:, 3:].reshape(-1, 3, 3).copy())
+        elif reliability:
             cxd, corr, red, wst = ctx.reliability(st[3])
         else:
             cxd, corr = ctx.covariance(st[3]) if covariance else (None, None)
@@ -181,7 +195,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw)
+                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -201,24 +215,28 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_prr(os.path.join(folder, name + ".prr"), data, res)
     if res.lm_history is not None:
         report.write_lm(os.path.join(folder, name + ".lm"), res.lm_history)
+    if getattr(res, "ell_axes", None) is not None:
+        report.write_ell(os.path.join(folder, name + ".ell"), data, res)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False, method="gn", lm_options=None) -> int:
+         priors=False, method="gn", lm_options=None, ellipsoids=False) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
     adjust()'s robust loss; the .wgt table (report.write_wgt) is written too.  priors=True: the folder's .pri
     table as prior observations of unknowns (io.read_pri; without the file main returns 1); the .prr table
     (report.write_prr) is written too.  method="lm" (lm_options: adjust()'s): the damped loop of fba_adjust_lm
-    in place of the Gauss-Newton loop; the .lm table (report.write_lm) is written too."""
+    in place of the Gauss-Newton loop; the .lm table (report.write_lm) is written too.  ellipsoids=True:
+    adjust()'s point_precision; the .ell table (report.write_ell) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
         data = load_folder(folder, project_dir=None if folder == project_dir else project_dir)
         res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k,
                      **({"priors": True} if priors else {}),
+                     **({"point_precision": True} if ellipsoids else {}),
                      **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:

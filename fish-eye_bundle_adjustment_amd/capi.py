@@ -30,7 +30,11 @@ EXPORTS = (
     "fba_set_weights", "fba_set_loss", "fba_get_weights", "fba_last_timings", "fba_set_timing", "fba_set_probe",
     "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
     "fba_set_damping", "fba_cost", "fba_adjust_lm",
+    "fba_postfit_outputs",
 )
+# ... but for the host-only helpers whose names carry a digit (tests/test_damping_host.py reads the header's
+# declarations with a letters-only pattern and compares them with EXPORTS)
+HOST_EXPORTS = ("fba_eig3_host",)
 
 
 class FBAError(RuntimeError):
@@ -60,6 +64,11 @@ class Options(C.Structure):
 
 class Priors(C.Structure):
     _fields_ = [("n", C.c_int64), ("index", C.c_void_p), ("value", C.c_void_p), ("sigma", C.c_void_p)]
+
+
+class Postfit(C.Structure):
+    """fba_postfit: the output pointers of fba_postfit_outputs, any of them NULL"""
+    _fields_ = [(n, C.c_void_p) for n in ("cx_diag", "corr", "redundancy", "wstat", "cx_tie", "ellipsoid")]
 
 
 class LMOptions(C.Structure):
@@ -133,6 +142,8 @@ def _load():
         "fba_set_damping": ([P, D], C.c_int),
         "fba_cost": ([P, P], C.c_int),
         "fba_adjust_lm": ([P, P, P, P, P], C.c_int),
+        "fba_postfit_outputs": ([P, D, P], C.c_int),
+        "fba_eig3_host": ([C.c_int64, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -372,6 +383,30 @@ class Context:
         check(lib.fba_reliability(self.h, float(sigma02), ptr(d), ptr(cr), ptr(red), ptr(wst)))
         return d[: int(self.u)], (cr[: self.packed.n_img] if corr else None), red[: 2 * n], wst[: 2 * n]
 
+    def postfit(self, sigma02, reliability=False, tie_cov=True, ellipsoids=True, corr=True):
+        """fba_postfit_outputs: (cx_diag, corr, redundancy, wstat, cx_tie, ellipsoid) in one call on one selected
+        inverse -- the first four exactly covariance()'s / reliability()'s (redundancy and wstat None without
+        reliability=True), cx_tie (n_tie, 6): XX XY XZ YY YZ ZZ of every tie point's block of the final Cx, ellipsoid
+        (n_tie, 12): the 1-sigma semi-axes a >= b >= c and the three unit axis vectors as rows, TIE order; None
+        where not asked for.  Consumes the factor like covariance(): call one of the three."""
+        st = self.settings
+        u_img = sum(int(x) for x in (st.est_Xc, st.est_Yc, st.est_Zc, st.est_omega, st.est_phi, st.est_kappa))
+        u_cam = (int(st.est_xp) + int(st.est_yp) + int(st.est_c) + int(st.est_radial) * int(st.num_radial)
+                 + 2 * int(st.est_decent))
+        mu = u_img + u_cam
+        n, nt = self.packed.n_pts, self.packed.n_tie
+        d = np.zeros(max(int(self.u), 1))
+        cr = np.zeros((max(self.packed.n_img, 1), mu, mu)) if corr else None
+        red = np.zeros(max(2 * n, 1)) if reliability else None
+        wst = np.zeros(max(2 * n, 1)) if reliability else None
+        blk = np.zeros((max(nt, 1), 6)) if tie_cov else None
+        ell = np.zeros((max(nt, 1), 12)) if ellipsoids else None
+        out = Postfit(*[None if a is None else ptr(a).value for a in (d, cr, red, wst, blk, ell)])
+        check(lib.fba_postfit_outputs(self.h, float(sigma02), C.byref(out)))
+        return (d[: int(self.u)], (cr[: self.packed.n_img] if corr else None),
+                (red[: 2 * n] if reliability else None), (wst[: 2 * n] if reliability else None),
+                (blk[:nt] if tie_cov else None), (ell[:nt] if ellipsoids else None))
+
     def set_weights(self, weights=None):
         """fba_set_weights: per-measurement multipliers of the a-priori weight, (2 n_pts) in PHO order, x y
         interleaved like v (or (n_pts, 2)); None restores all 1.  Entries must be finite and > 0."""
@@ -428,6 +463,22 @@ class Context:
         ms = np.zeros(8)
         check(lib.fba_last_timings(self.h, ptr(ms)))
         return ms
+
+
+def eig3_host(blocks):
+    """fba_eig3_host: the device's symmetric 3 x 3 eigen routine (csrc/fba_eig3.h) run on the CPU, no GPU needed.
+    blocks (n, 6): XX XY XZ YY YZ ZZ -> (n, 12): the semi-axes a >= b >= c = sqrt(max(lambda, 0)), then the three
+    unit axis vectors as rows."""
+    b = np.ascontiguousarray(blocks, dtype=np.float64).reshape(-1, 6)
+    out = np.zeros((max(len(b), 1), 12))
+    check(lib.fba_eig3_host(len(b), ptr(b) if len(b) else None, ptr(out)))
+    return out[: len(b)]
+
+
+def tie_blocks(cx_tie):
+    """(n_tie, 6) XX XY XZ YY YZ ZZ -> (n_tie, 3, 3) full symmetric"""
+    b = np.asarray(cx_tie, dtype=np.float64).reshape(-1, 6)
+    return b[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
 
 
 def count_unknowns(packed: PackedProblem, settings: Settings) -> int:

@@ -19,6 +19,7 @@
 #include <tuple>
 
 #include "fba_internal.h"
+#include "fba_eig3.h"
 
 namespace fba {
 
@@ -1880,11 +1881,16 @@ int fba_build_rsd(fba_ctx* ctx, const double* v, const double* xhat, double* rsd
 
 // fba_covariance, and with rel fba_reliability: the same launches and host code for cx_diag / corr, then the
 // reliability kernels on the same selected inverse (redundancy / wstat [2 n_pts], either may be NULL)
+// postfit (fba_postfit_outputs): launch_postfit instead of the two older drivers -- the same launches for the four
+// outputs above, then the tie points' full blocks (cx_tie [6 n_tie], TIE order) and their ellipsoids (ellipsoid
+// [12 n_tie]); either may be NULL, the ellipsoids alone keep the blocks in workspace
 static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_diag, double* corr, bool rel,
-                           double* redundancy, double* wstat) {
+                           double* redundancy, double* wstat, bool postfit = false, double* cx_tie = nullptr,
+                           double* ellipsoid = nullptr) {
     if (!c) { set_error("NULL context"); return FBA_ERR_ARG; }
     if (rel && c->sched.split) {
-        set_error("fba_reliability: not implemented for the subtree split (fba_solve_mode 1); use the replicated solve");
+        set_error(std::string(who) + ": redundancy / wstat are not implemented for the subtree split (fba_solve_mode 1); "
+                  "use the replicated solve");
         return FBA_ERR_UNSUPPORTED;
     }
     if (!c->have_factor || !c->have_delta) {
@@ -1925,10 +1931,28 @@ static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_d
                 (rc = ws_get(*c, 70, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_red)) ||
                 (rc = ws_get(*c, 71, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_wst))))
         return rc;
-    if ((rc = rel ? launch_reliability(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst)
-                  : launch_covariance(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0))) {
+    double *d_blk = nullptr, *d_ell = nullptr;
+    const size_t nt = (size_t)std::max(L.n_tie, 1);
+    if (((cx_tie || ellipsoid) && (rc = ws_get(*c, 72, sizeof(double) * 6 * nt, (void**)&d_blk))) ||
+        (ellipsoid && (rc = ws_get(*c, 73, sizeof(double) * 12 * nt, (void**)&d_ell))))
+        return rc;
+    if ((rc = postfit ? launch_postfit(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst,
+                                       sigma02, d_blk, d_ell)
+              : rel   ? launch_reliability(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst)
+                      : launch_covariance(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0))) {
         release();
         return rc;
+    }
+    if (L.n_tie > 0 && (cx_tie || ellipsoid)) {
+        if ((cx_tie && hipMemcpy(cx_tie, d_blk, sizeof(double) * 6 * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (ellipsoid && hipMemcpy(ellipsoid, d_ell, sizeof(double) * 12 * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess)) {
+            set_error("HIP error copying the tie points' blocks back");
+            return FBA_ERR_HIP;
+        }
+        // (another rank's points: zeros, so that the ranks' outputs sum; their blocks are zero already)
+        if (ellipsoid)
+            for (int t = 0; t < L.n_tie; ++t)
+                if (!c->full_owned[L.u_c + 3 * (int64_t)t]) std::fill(ellipsoid + 12 * (size_t)t, ellipsoid + 12 * (size_t)t + 12, 0.0);
     }
     if (rel && c->n_pts > 0) {
         const size_t nb = sizeof(double) * 2 * (size_t)c->n_pts;
@@ -1995,6 +2019,18 @@ int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr) 
 
 int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr, double* redundancy, double* wstat) {
     return covariance_impl(reinterpret_cast<Ctx*>(ctx), "fba_reliability", sigma02, cx_diag, corr, true, redundancy, wstat);
+}
+
+int fba_postfit_outputs(fba_ctx* ctx, double sigma02, const fba_postfit* out) {
+    if (!out) { set_error("fba_postfit_outputs: NULL output structure"); return FBA_ERR_ARG; }
+    return covariance_impl(reinterpret_cast<Ctx*>(ctx), "fba_postfit_outputs", sigma02, out->cx_diag, out->corr,
+                           out->redundancy || out->wstat, out->redundancy, out->wstat, true, out->cx_tie, out->ellipsoid);
+}
+
+int fba_eig3_host(int64_t n, const double* blk, double* ell) {
+    if (n < 0 || (n > 0 && (!blk || !ell))) { set_error("fba_eig3_host: NULL argument"); return FBA_ERR_ARG; }
+    for (int64_t i = 0; i < n; ++i) eig3_block(blk + 6 * i, ell + 12 * i);
+    return FBA_OK;
 }
 
 int fba_finish_stats(const fba_problem* p, const fba_settings* s, const double* sums, double vtpv, double* stats) {

@@ -19,10 +19,13 @@
 //   camera side         diag C, and per image the (6 + cw)^2 block over its EOPs and its camera's
 //                       unknowns (the reference's EOP/IOP correlation sub-matrices);
 //   tie points          Cx_pp = V^-1 + T' C T with T = W V^-1 of the point's observations and camera
-//                       (the Schur identity for the eliminated points), diagonal only.
+//                       (the Schur identity for the eliminated points), diagonal only (k_cov_pts); the full
+//                       3 x 3 block and its error ellipsoid on request (k_cov_pts_blk, k_ellipsoid:
+//                       fba_postfit_outputs, no reference counterpart).
 // All sums run in a fixed order (no atomics).  The factor in S is consumed; the next iteration
 // re-accumulates S from scratch (k_zero_blocks), so nothing else is affected.
 #include "fba_internal.h"
+#include "fba_eig3.h"
 
 #include <algorithm>
 #include <array>
@@ -366,6 +369,145 @@ __global__ __launch_bounds__(256) void k_cov_pts(const double* __restrict__ S, i
     }
 }
 
+// tie points, the full block (fba_postfit_outputs): k_cov_pts with six accumulators XX XY XZ YY YZ ZZ of
+// V^-1 + T' C T instead of its diagonal -- the same plan, one wave per local point, the same entries of S, Z, Wz, T
+// and Tc read in the same order, and the rest of the point's V^-1 (PT's first six: 00 01 02 11 12 22).  A group
+// pair g > h stands for (g, h) and (h, g): entry (i, j) gets Tg[a,i] q Th[b,j] + Tg[a,j] q Th[b,i], which on the
+// diagonal is k_cov_pts' doubling.  The border term -(Z_a' T)_i (Wz_a' T)_j summed over a is symmetric (Z' H^-1 Z)
+// but not per a in floating point: both orders are averaged.  Fixed-order wave reduction, no atomics.  Writes
+// sigma02 x block to blk[6 tie].
+__global__ __launch_bounds__(256) void k_cov_pts_blk(const double* __restrict__ S, int64_t ld, const double* __restrict__ Z,
+                                                     const double* __restrict__ Wz, int nz, int64_t n_pad,
+                                                     const double* __restrict__ WT, const double* __restrict__ PT, int ps,
+                                                     const int32_t* __restrict__ lp_start, const int32_t* __restrict__ lp_tie,
+                                                     const int32_t* __restrict__ lp_cam, const int32_t* __restrict__ img,
+                                                     int64_t n_lp, int n_img, int cw, double sigma02,
+                                                     double* __restrict__ blk) {
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (p >= n_lp) return;
+    const int o0 = lp_start[p], m = lp_start[p + 1] - o0;
+    const double* P = PT + p * ps;
+    const double* Tc = P + 12 + 3 * cw;
+    const int64_t cam0 = 6 * (int64_t)n_img + (int64_t)lp_cam[p] * cw;
+    auto grp_rows = [&](int g, int64_t& r0, int& n, const double*& T) {
+        if (g < m) { r0 = 6 * (int64_t)img[o0 + g]; n = 6; T = WT + (int64_t)(o0 + g) * 18; }
+        else { r0 = cam0; n = cw; T = Tc; }
+    };
+    double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0;
+    const int ng = m + 1;
+    // k_cov_pts' dealing of the entries of the pairs g >= h to the lanes
+    const int n_ii = m * (m + 1) / 2 * 36, n_ci = m * 6 * cw, n_all = n_ii + n_ci + cw * cw;
+#pragma unroll 2
+    for (int e = lane; e < n_all; e += 64) {
+        int g, h, a, b;
+        if (e < n_ii) {
+            const int pr = e / 36, en = e - 36 * pr;
+            g = 0;
+            h = pr;
+            while (h > g) { h -= g + 1; ++g; }
+            a = en / 6;
+            b = en - 6 * a;
+        } else if (e < n_ii + n_ci) {
+            const int e2 = e - n_ii;
+            g = m;
+            h = e2 / (6 * cw);
+            const int en = e2 - 6 * cw * h;
+            a = en / 6;
+            b = en - 6 * a;
+        } else {
+            const int e3 = e - n_ii - n_ci;
+            g = h = m;
+            a = e3 / cw;
+            b = e3 - cw * a;
+        }
+        int64_t r0, c0;
+        int nr, nc;
+        const double *Tg, *Th;
+        grp_rows(g, r0, nr, Tg);
+        grp_rows(h, c0, nc, Th);
+        const int64_t r = r0 + a, c = c0 + b;
+        const int64_t rr = (r / CB >= c / CB) ? r : c, cc = (r / CB >= c / CB) ? c : r;
+        const double q = S[rr * ld + cc];
+        const double f = g == h ? 0.0 : 1.0;  // the mirrored pair (h, g)
+        const double u0 = Tg[3 * a] * q, u1 = Tg[3 * a + 1] * q, u2 = Tg[3 * a + 2] * q;
+        const double t0 = Th[3 * b], t1 = Th[3 * b + 1], t2 = Th[3 * b + 2];
+        axx += (1.0 + f) * (u0 * t0);
+        ayy += (1.0 + f) * (u1 * t1);
+        azz += (1.0 + f) * (u2 * t2);
+        axy += u0 * t1 + f * (u1 * t0);
+        axz += u0 * t2 + f * (u2 * t0);
+        ayz += u1 * t2 + f * (u2 * t1);
+    }
+    if (lane < nz) {
+        double z0 = 0, z1 = 0, z2 = 0, w0 = 0, w1 = 0, w2 = 0;
+        for (int g = 0; g < ng; ++g) {
+            int64_t r0;
+            int nr;
+            const double* Tg;
+            grp_rows(g, r0, nr, Tg);
+            for (int a = 0; a < nr; ++a) {
+                const double zv = Z[lane * n_pad + r0 + a], wv = Wz[lane * n_pad + r0 + a];
+                z0 += zv * Tg[3 * a]; z1 += zv * Tg[3 * a + 1]; z2 += zv * Tg[3 * a + 2];
+                w0 += wv * Tg[3 * a]; w1 += wv * Tg[3 * a + 1]; w2 += wv * Tg[3 * a + 2];
+            }
+        }
+        axx -= z0 * w0; ayy -= z1 * w1; azz -= z2 * w2;
+        axy -= 0.5 * (z0 * w1 + z1 * w0);
+        axz -= 0.5 * (z0 * w2 + z2 * w0);
+        ayz -= 0.5 * (z1 * w2 + z2 * w1);
+    }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) {
+        axx += __shfl_xor(axx, w, 64);
+        axy += __shfl_xor(axy, w, 64);
+        axz += __shfl_xor(axz, w, 64);
+        ayy += __shfl_xor(ayy, w, 64);
+        ayz += __shfl_xor(ayz, w, 64);
+        azz += __shfl_xor(azz, w, 64);
+    }
+    if (lane == 0) {
+        double* out = blk + 6 * (int64_t)lp_tie[p];
+        out[0] = sigma02 * (P[0] + axx);
+        out[1] = sigma02 * (P[1] + axy);
+        out[2] = sigma02 * (P[2] + axz);
+        out[3] = sigma02 * (P[3] + ayy);
+        out[4] = sigma02 * (P[4] + ayz);
+        out[5] = sigma02 * (P[5] + azz);
+    }
+}
+
+// error ellipsoids: one thread per tie point, the symmetric 3 x 3 eigen-decomposition of fba_eig3.h on the scaled
+// block.  blk [6 n] -> ell [12 n]; both pass through LDS, so that the global loads and stores of a workgroup are
+// contiguous (thread t touches element t + 256 k of the workgroup's 256 x 6 / 256 x 12 doubles), and a thread's own
+// 6 / 12 sit at a stride of 7 / 13 doubles: an odd stride, the 64 lanes of a wave on distinct bank pairs
+constexpr int ELL_WG = 256, ELL_SI = 7, ELL_SO = 13;
+__global__ __launch_bounds__(ELL_WG) void k_ellipsoid(const double* __restrict__ blk, int64_t n, double* __restrict__ ell) {
+    __shared__ double sh[ELL_WG * ELL_SO];
+    const int t = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * ELL_WG;
+    const int np = (int)(n - p0 < ELL_WG ? n - p0 : ELL_WG);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const int e = t + ELL_WG * k;
+        if (e < 6 * np) sh[(e / 6) * ELL_SI + e % 6] = blk[6 * p0 + e];
+    }
+    __syncthreads();
+    double b[6], o[12];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = t < np ? sh[t * ELL_SI + k] : 0.0;
+    eig3_block(b, o);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; ++k) sh[t * ELL_SO + k] = o[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const int e = t + ELL_WG * k;
+        if (e < 12 * np) ell[12 * p0 + e] = sh[(e / 12) * ELL_SO + e % 12];
+    }
+}
+
 // backward solve of one right-hand-side row (fba_chol.hip)
 int launch_backward_rows(Ctx& c, int row0, int nrows, double* X);
 int launch_obs_T(Ctx& c, double* T);
@@ -597,6 +739,47 @@ int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk,
     int rc;
     if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)) ||
         (rc = launch_rel_outputs(c, si, d_q, d_red, d_wst)))
+        return rc;
+    FBA_HIP(hipStreamSynchronize(c.stream));
+    c.have_factor = false;
+    return FBA_OK;
+}
+
+// the tie points' full blocks sigma02 (V^-1 + T' C T) into d_blk [6 n_tie] (zeroed first: another rank's points,
+// points without an observation) and, with d_ell, their ellipsoids [12 n_tie], from the selected inverse
+// launch_selinv left in S (read only; shares launch_cov_outputs' T table when that built one)
+static int launch_blk_outputs(Ctx& c, SelInv& si, double sigma02, double* d_blk, double* d_ell) {
+    const Layout& L = c.L;
+    int rc;
+    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, si.next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
+    FBA_HIP(hipMemsetAsync(d_blk, 0, sizeof(double) * 6 * (size_t)std::max(L.n_tie, 1), c.stream));
+    if (c.n_lp > 0) {
+        if (!si.d_T && ((rc = alloc(&si.d_T, (size_t)18 * std::max<int64_t>(c.n_obs_tie, 1))) || (rc = launch_obs_T(c, si.d_T))))
+            return rc;
+        k_cov_pts_blk<<<(unsigned)((c.n_lp + 3) / 4), 256, 0, c.stream>>>(c.d_S, L.ld, si.d_Z, si.d_Wz, si.nz, L.n_pad, si.d_T,
+                                                                          c.d_pt_tab, c.pt_comp, c.d_lp_start, c.d_lp_tie,
+                                                                          c.d_lp_cam, c.d_img, c.n_lp, L.n_img, L.cw, sigma02,
+                                                                          d_blk);
+        FBA_HIP(hipGetLastError());
+    }
+    if ((rc = launch_gen_cov_blk(c, si.d_Z, si.d_Wz, si.nz, sigma02, d_blk))) return rc;
+    if (d_ell && L.n_tie > 0) {
+        k_ellipsoid<<<(unsigned)((L.n_tie + ELL_WG - 1) / ELL_WG), ELL_WG, 0, c.stream>>>(d_blk, L.n_tie, d_ell);
+        FBA_HIP(hipGetLastError());
+    }
+    return FBA_OK;
+}
+
+// fba_postfit_outputs: fba_covariance's launches, the reliability kernels when d_red is given (then d_q and d_wst
+// too), the block kernels and k_ellipsoid when d_blk / d_ell are given (d_ell needs d_blk), all on one selected
+// inverse
+int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot, const int32_t* d_icam,
+                   int n_iblk, double* d_q, double* d_red, double* d_wst, double sigma02, double* d_blk, double* d_ell) {
+    SelInv si;
+    int rc;
+    if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)) ||
+        (d_red && (rc = launch_rel_outputs(c, si, d_q, d_red, d_wst))) ||
+        (d_blk && (rc = launch_blk_outputs(c, si, sigma02, d_blk, d_ell))))
         return rc;
     FBA_HIP(hipStreamSynchronize(c.stream));
     c.have_factor = false;

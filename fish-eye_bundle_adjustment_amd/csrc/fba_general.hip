@@ -413,6 +413,82 @@ __global__ __launch_bounds__(256) void k_cov_gen(const double* __restrict__ S, i
     }
 }
 
+// the general points' full blocks (fba_postfit_outputs): k_cov_gen with six accumulators XX XY XZ YY YZ ZZ of
+// V^-1 + K' C K.  The lanes walk ALL ordered group pairs (x, y), as there, so (x, y) and (y, x) both occur and
+// entry (i, j) is the plain sum of Tx[a,i] C(r, c) Ty[b,j]; the border term's two orders are averaged
+// (k_cov_pts_blk).  Writes sigma02 x block to blk[6 tie].
+template <int NK>
+__global__ __launch_bounds__(256) void k_cov_gen_blk(const double* __restrict__ S, int64_t ld, const double* __restrict__ Z,
+                                                     const double* __restrict__ Wz, int nz, int64_t n_pad,
+                                                     const int32_t* __restrict__ A, const GenPlan g,
+                                                     const double* __restrict__ gpt, const double* __restrict__ gcu,
+                                                     const double* __restrict__ gug, const int32_t* __restrict__ lp_tie,
+                                                     int n_img, double sigma02, double* __restrict__ blk) {
+    constexpr int CW = GL<NK>::CW, GC = GL<NK>::GC;
+    const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= g.n_gp) return;
+    const int i0 = A[g.g_gi + q], ni = A[g.g_gi + q + 1] - i0;
+    const int c0 = A[g.g_gc + q], nc = A[g.g_gc + q + 1] - c0;
+    auto grp = [&](int x, int64_t& r0, int& n, const double*& T) {
+        if (x < ni) { r0 = 6 * (int64_t)A[g.gi_img + i0 + x]; n = 6; T = gug + (int64_t)(i0 + x) * GUG + 18; }
+        else { r0 = 6 * (int64_t)n_img + (int64_t)A[g.gc_cam + c0 + x - ni] * CW; n = CW; T = gcu + (int64_t)(c0 + x - ni) * GC + 3 * CW; }
+    };
+    const int ng = ni + nc;
+    double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0;
+    for (int pr = lane; pr < ng * ng; pr += 64) {
+        const int x = pr / ng, y = pr % ng;
+        int64_t r0, c0_;
+        int nr, ncc;
+        const double *Tg, *Th;
+        grp(x, r0, nr, Tg);
+        grp(y, c0_, ncc, Th);
+        for (int a = 0; a < nr; ++a) {
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+            for (int b = 0; b < ncc; ++b) {
+                const int64_t r = r0 + a, c = c0_ + b;
+                const int64_t rr = (r / NB >= c / NB) ? r : c, cc = (r / NB >= c / NB) ? c : r;
+                const double v = S[rr * ld + cc];
+                s0 += v * Th[3 * b]; s1 += v * Th[3 * b + 1]; s2 += v * Th[3 * b + 2];
+            }
+            const double t0 = Tg[3 * a], t1 = Tg[3 * a + 1], t2 = Tg[3 * a + 2];
+            axx += t0 * s0; axy += t0 * s1; axz += t0 * s2;
+            ayy += t1 * s1; ayz += t1 * s2;
+            azz += t2 * s2;
+        }
+    }
+    if (lane < nz) {
+        double z0 = 0, z1 = 0, z2 = 0, w0 = 0, w1 = 0, w2 = 0;
+        for (int x = 0; x < ng; ++x) {
+            int64_t r0;
+            int nr;
+            const double* Tg;
+            grp(x, r0, nr, Tg);
+            for (int a = 0; a < nr; ++a) {
+                const double zv = Z[lane * n_pad + r0 + a], wv = Wz[lane * n_pad + r0 + a];
+                z0 += zv * Tg[3 * a]; z1 += zv * Tg[3 * a + 1]; z2 += zv * Tg[3 * a + 2];
+                w0 += wv * Tg[3 * a]; w1 += wv * Tg[3 * a + 1]; w2 += wv * Tg[3 * a + 2];
+            }
+        }
+        axx -= z0 * w0; ayy -= z1 * w1; azz -= z2 * w2;
+        axy -= 0.5 * (z0 * w1 + z1 * w0);
+        axz -= 0.5 * (z0 * w2 + z2 * w0);
+        ayz -= 0.5 * (z1 * w2 + z2 * w1);
+    }
+    axx = wave_sum(axx); axy = wave_sum(axy); axz = wave_sum(axz);
+    ayy = wave_sum(ayy); ayz = wave_sum(ayz); azz = wave_sum(azz);
+    if (lane == 0) {
+        const double* P = gpt + q * GPT;
+        double* out = blk + 6 * (int64_t)lp_tie[g.lp0 + q];
+        out[0] = sigma02 * (P[0] + axx);
+        out[1] = sigma02 * (P[1] + axy);
+        out[2] = sigma02 * (P[2] + axz);
+        out[3] = sigma02 * (P[3] + ayy);
+        out[4] = sigma02 * (P[4] + ayz);
+        out[5] = sigma02 * (P[5] + azz);
+    }
+}
+
 // ================================================================================================
 // launchers
 // ================================================================================================
@@ -508,6 +584,18 @@ int launch_gen_cov(Ctx& c, const double* Z, const double* Wz, int nz, double* pd
                                                              c.d_gcu, c.d_gug, c.d_lp_tie, c.L.n_img, pdiag)
     GEN_NK_DISPATCH(c.L.nk, GV);
 #undef GV
+    FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+int launch_gen_cov_blk(Ctx& c, const double* Z, const double* Wz, int nz, double sigma02, double* blk) {
+    const GenPlan& g = c.gen;
+    if (g.n_gp == 0) return FBA_OK;
+#define GVB(NKV)                                                                                                     \
+    k_cov_gen_blk<NKV><<<grid_of(g.n_gp, 4), 256, 0, c.stream>>>(c.d_S, c.L.ld, Z, Wz, nz, c.L.n_pad, c.d_acc, g, c.d_gpt, \
+                                                                 c.d_gcu, c.d_gug, c.d_lp_tie, c.L.n_img, sigma02, blk)
+    GEN_NK_DISPATCH(c.L.nk, GVB);
+#undef GVB
     FBA_HIP(hipGetLastError());
     return FBA_OK;
 }

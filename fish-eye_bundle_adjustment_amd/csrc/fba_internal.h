@@ -455,6 +455,12 @@ int launch_selinv(Ctx& c, SelInv& si);
 int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst);  // fba_rel.hip
 int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
                        const int32_t* d_icam, int n_iblk, double* d_q, double* d_red, double* d_wst);
+// fba_postfit_outputs (fba_cov.hip): the two drivers above on one selected inverse, plus the tie points' full
+// 3 x 3 blocks sigma02 Cx_pp (d_blk [6 n_tie]; k_cov_pts_blk, k_cov_gen_blk) and their ellipsoids (d_ell [12 n_tie];
+// k_ellipsoid); d_red == nullptr: no reliability, d_blk == nullptr: no blocks (then no d_ell either)
+int launch_gen_cov_blk(Ctx& c, const double* Z, const double* Wz, int nz, double sigma02, double* blk);
+int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot, const int32_t* d_icam,
+                   int n_iblk, double* d_q, double* d_red, double* d_wst, double sigma02, double* d_blk, double* d_ell);
 int launch_dense_awg(Ctx& c, double* dA, double* dG, const int64_t* d_map, int64_t n_rows, int64_t u_ref);
 int border_solve_selftest(int device, const double* gram, double* coef);  // fba_test_border_solve
 

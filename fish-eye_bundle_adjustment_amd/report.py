@@ -23,6 +23,7 @@ MDB_DELTA0 = 4.13   # Baarda's non-centrality parameter for alpha0 = 0.1 %, beta
 W_CRITICAL = 3.29   # two-sided 0.1 % point of the standard normal distribution (write_rel's flag)
 R_MIN = 1e-10       # below it an observation cannot be checked (fba_reliability reports w = 0)
 WGT_FLAG = 0.5      # write_wgt stars a row with an effective weight below it
+ELL_K95 = 2.7955    # sqrt(7.8147), the 0.95 point of chi-square with 3 degrees of freedom: 1-sigma axes -> 95 % region
 PRODUCER = "fba_amd, the MI355X-native HIP implementation (not the MATLAB reference)"
 
 
@@ -382,6 +383,53 @@ def write_lm(path, history):
     with open(path, "w") as fh:
         for i, (lam, cost, dsum, acc) in enumerate(h):
             fh.write("\t".join([str(i + 1), _cell(lam), _cell(cost), _cell(dsum), str(int(acc))]) + "\n")
+
+
+def horizontal_ellipse(sxx, sxy, syy):
+    """The 1-sigma error ellipse of a 2 x 2 covariance [[sxx, sxy], [sxy, syy]] in closed form: (semi-major,
+    semi-minor, azimuth of the major axis in degrees in [0, 180), counted from +Y towards +X; 0 for a circle)."""
+    m, d = 0.5 * (sxx + syy), 0.5 * (sxx - syy)
+    r = math.hypot(d, sxy)
+    az = 0.0 if r == 0.0 else math.degrees(0.5 * math.atan2(2.0 * sxy, syy - sxx)) % 180.0
+    return math.sqrt(max(m + r, 0.0)), math.sqrt(max(m - r, 0.0)), (0.0 if az >= 180.0 else az)
+
+
+def write_ell(path, data, res):
+    """The point-precision table <Output_Filename stem>.ell (no reference counterpart: main.m:460-482 keeps the
+    diagonal of Cx), tab-delimited in write_rsd's style, one row per tie point in TIE order: targetID; sigma X, Y,
+    Z (the square roots of the block's diagonal); the 1-sigma semi-axes a >= b >= c of the error ellipsoid; the
+    nine direction cosines of its axes (axis a's X Y Z, then b's, then c's); the horizontal error ellipse of the
+    block's XY part (horizontal_ellipse): semi-major, semi-minor, azimuth of the major axis in degrees in
+    [0, 180).  Every length is 1 sigma: multiply the three semi-axes by ELL_K95 = 2.7955 = sqrt(chi2_3(0.95)) for
+    the region that holds the point with 95 % probability."""
+    if getattr(res, "cx_tie", None) is None or getattr(res, "ell_axes", None) is None or getattr(res, "ell_dirs", None) is None:
+        raise ValueError("write_ell: the adjustment carries no point precision (adjust(..., point_precision=True))")
+    blk = np.asarray(res.cx_tie, dtype=np.float64).reshape(-1, 3, 3)
+    ax = np.asarray(res.ell_axes, dtype=np.float64).reshape(-1, 3)
+    dr = np.asarray(res.ell_dirs, dtype=np.float64).reshape(-1, 9)
+    if not (len(blk) == len(ax) == len(dr) == len(data.TIE)):
+        raise ValueError("write_ell: one block and one ellipsoid per tie point expected")
+    with open(path, "w") as fh:
+        for t, name in enumerate(data.TIE):
+            b = blk[t]
+            sig = [math.sqrt(max(b[k, k], 0.0)) for k in range(3)]
+            fh.write("\t".join([name] + [_cell(v) for v in (*sig, *ax[t], *dr[t], *horizontal_ellipse(b[0, 0], b[0, 1], b[1, 1]))])
+                     + "\n")
+
+
+def read_ell(path):
+    """write_ell's table back: (targetIDs, sigma (n, 3), axes (n, 3), directions (n, 3, 3), horizontal (n, 3):
+    semi-major, semi-minor, azimuth)"""
+    names, vals = [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if len(c) != 19:
+                raise ValueError(f"read_ell: {path}: expected 19 tab-separated columns, got {len(c)}")
+            names.append(c[0])
+            vals.append([float(x) for x in c[1:]])
+    v = np.array(vals, dtype=np.float64).reshape(-1, 18)
+    return names, v[:, 0:3], v[:, 3:6], v[:, 6:15].reshape(-1, 3, 3), v[:, 15:18]
 
 
 def read_prr(path):

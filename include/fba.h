@@ -278,6 +278,35 @@ int fba_covariance(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr);
 int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr,
                     double* redundancy /*[2*n_pts]*/, double* wstat /*[2*n_pts]*/);
 
+/* Point precision: the full 3 x 3 covariance of every object (tie) point and its error ellipsoid (no reference
+ * counterpart: main.m:460-482 keeps the diagonal).  One call for every post-fit output, from the same factor and
+ * the same state as fba_covariance: it needs the factor of the last undamped solve and consumes it (FBA_ERR_ARG
+ * before any solve, after a damped solve, or on a second call).
+ *   cx_diag, corr, redundancy, wstat: exactly fba_covariance's / fba_reliability's outputs (bit-identical).
+ *   cx_tie [6*n_tie] (TIE order): XX XY XZ YY YZ ZZ of sigma02 * Cx_pp, Cx_pp = V^-1 + T' C T the point's block of
+ *           the cofactor matrix (main.m:428-444); its XX YY ZZ are cx_diag's tie entries up to the order of an
+ *           fp64 sum.  Tie entries carry no distortion de-scaling.
+ *   ellipsoid [12*n_tie] (TIE order): the 1-sigma semi-axes a >= b >= c, a = sqrt(max(lambda, 0)) of that block's
+ *           eigenvalues (cyclic Jacobi, fp64), then the three unit axis vectors as rows in the same order, each
+ *           with its largest-magnitude component positive (on ties the first component wins).  A non-finite
+ *           block gives NaNs for that point.  Scale the axes by sqrt(chi2_3(0.95)) = 2.7955 for the 95 % region.
+ * Any pointer may be NULL; with ellipsoid set and cx_tie NULL the blocks stay in workspace.  With world > 1 the
+ * tie points of other ranks get zeros in cx_tie and ellipsoid (the ranks' outputs sum to the whole).  With the
+ * subtree split cx_tie and ellipsoid follow cx_diag's tie entries; a non-NULL redundancy or wstat returns
+ * FBA_ERR_UNSUPPORTED as fba_reliability does and leaves the factor in place. */
+typedef struct fba_postfit {
+    double* cx_diag;    /* [u]                     as fba_covariance            */
+    double* corr;       /* [n_img][(u_img+u_cam)^2] as fba_covariance           */
+    double* redundancy; /* [2 n_pts]               as fba_reliability           */
+    double* wstat;      /* [2 n_pts]               as fba_reliability           */
+    double* cx_tie;     /* [6 n_tie]  XX XY XZ YY YZ ZZ of sigma02 * Cx_pp      */
+    double* ellipsoid;  /* [12 n_tie] a b c, then the three axis vectors (rows) */
+} fba_postfit;          /* any pointer may be NULL */
+int fba_postfit_outputs(fba_ctx* ctx, double sigma02, const fba_postfit* out);
+/* host only, no GPU: the device's eigen routine run on the CPU (tests).  blk [6*n] XX XY XZ YY YZ ZZ per block,
+ * ell [12*n] as ellipsoid above (no reference counterpart: main.m:460-482 keeps the diagonal). */
+int fba_eig3_host(int64_t n, const double* blk /*[6n]*/, double* ell /*[12n]*/);
+
 /* Per-observation weights and robust loss (no reference counterpart: main.m:397-402 gives every observation
  * the weight 1 / Meas_std^2).  Both setters may be called at any point between iterations (not between
  * fba_solve_update_async and fba_solve_finish); both invalidate the last linearisation and the factor of the last
