@@ -245,6 +245,10 @@ static int create(const fba_problem* p, const fba_settings* s, const fba_options
     c->set = *s;
     c->opt = opt;
     c->force_sync = getenv("FBA_SYNC") && atoi(getenv("FBA_SYNC")) != 0;  // (read per context)
+    // the order of k_lin_reduce's (D) task queue: 1 camera-image-pair, 2 image-pair-camera, 3 image-camera-pair;
+    // anything else the default.  The results do not depend on it (tests/test_gpu_lr_queue.py)
+    c->lr_order = getenv("FBA_LR_ORDER") ? atoi(getenv("FBA_LR_ORDER")) : 0;
+    if (c->lr_order < 0 || c->lr_order > 3) c->lr_order = 0;
     c->n_pts = p->n_pts;
     Layout& L = c->L;
     // camera-side order of the images: nested dissection with padding slots (fba_order.cpp)
@@ -1032,19 +1036,23 @@ static int accumulate_body(Ctx* c) {
         std::vector<uint64_t> tp(8 * c->n_chunks_lr);
         FBA_HIP(hipMemcpyAsync(tp.data(), c->d_lrprof, sizeof(uint64_t) * tp.size(), hipMemcpyDeviceToHost, c->stream));
         FBA_HIP(hipStreamSynchronize(c->stream));
-        double ph[6] = {0, 0, 0, 0, 0, 0};
+        // stamps: 0 start, 1 model done, 2 points done, 3 (D) starts, 5 (D) and the camera sum done; 4, 6, 7 the
+        // finish of the last camera, image-key and pair-key task of (D)'s queue (0: the chunk had none)
+        double ph[7] = {0, 0, 0, 0, 0, 0, 0};
         uint64_t lo = UINT64_MAX, hi = 0;
         const double nch = (double)c->n_chunks_lr;
         for (int64_t ch = 0; ch < c->n_chunks_lr; ++ch) {
             const uint64_t* q = &tp[8 * ch];
-            for (int i = 0; i < 4; ++i) ph[i] += (double)(q[i + 1] - q[i]) * 0.01 / nch;
-            ph[4] += (double)(q[6] - q[4]) * 0.01 / nch;  // image keys
-            ph[5] += (double)(q[5] - q[6]) * 0.01 / nch;  // pair keys
+            for (int i = 0; i < 3; ++i) ph[i] += (double)(q[i + 1] - q[i]) * 0.01 / nch;
+            ph[3] += (double)(q[5] - q[3]) * 0.01 / nch;  // (D)
+            const int last[3] = {4, 6, 7};
+            for (int k = 0; k < 3; ++k) ph[4 + k] += (double)(std::max(q[last[k]], q[3]) - q[3]) * 0.01 / nch;
             lo = std::min(lo, q[0]);
             hi = std::max(hi, q[5]);
         }
-        fprintf(stderr, "[fba] k_lin_reduce per chunk (us): model %.2f points %.2f couplings %.2f stage+camera %.2f "
-                "image keys %.2f pair keys %.2f; span %.1f\n", ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], (double)(hi - lo) * 0.01);
+        fprintf(stderr, "[fba] k_lin_reduce per chunk (us): model %.2f points %.2f couplings %.2f queue %.2f "
+                "(last task done at: camera %.2f image keys %.2f pair keys %.2f; order %d); span %.1f\n", ph[0], ph[1],
+                ph[2], ph[3], ph[4], ph[5], ph[6], c->lr_order, (double)(hi - lo) * 0.01);
     }
     if (c->sched.split) {
         // subtree split: the top rows' accumulated diagonal (before k_border_rhs writes unit rows), the

@@ -503,6 +503,10 @@ struct LR {
 };
 
 constexpr int LR_THREADS = 512;  // observation phases use the first CHUNK_OBS threads, (D) all of them
+// the order in which (D)'s task queue hands out the three kinds of tasks (Ctx::lr_order, FBA_LR_ORDER;
+// 0 = the default): C camera entries, I image keys, P pair keys.  The results are the same bit for bit;
+// the default is the fastest measured (config 4 and the convergent scene)
+constexpr int LR_ORDER_CIP = 1, LR_ORDER_IPC = 2, LR_ORDER_ICP = 3, LR_ORDER_DEFAULT = LR_ORDER_IPC;
 
 template <int NK, int IKL, bool WH>
 __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
@@ -514,7 +518,8 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     double* __restrict__ ppart, double* __restrict__ ipart, double* __restrict__ cpart, int64_t u_c, int type,
     int cam_stride, unsigned eop_mask, unsigned cam_mask, double px, double py, uint64_t* __restrict__ tprof,
     int n_chunks, double* __restrict__ S, int64_t ld, const int32_t* __restrict__ zblk,
-    const int32_t* __restrict__ xoff, double* __restrict__ Ug, const Whiten wh, const double* __restrict__ damp) {
+    const int32_t* __restrict__ xoff, double* __restrict__ Ug, const Whiten wh, const double* __restrict__ damp,
+    int lr_order) {
     using LY = Lay<NK>;
     using R_ = LR<NK>;
     if ((int)blockIdx.x >= n_chunks) {  // tail workgroups: zero one 128x128 block of the factor's pattern
@@ -546,6 +551,11 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     double* Us = QE + CHUNK_OBS * ES;                  // [CHUNK_OBS][US]
     double* PP = Us + CHUNK_OBS * US;                  // [CP][PPS]
     double* camp = PP + R_::CP * PPS;                        // [CAM_SPLIT][NCAM] camera sub-range sums
+    // (the 512 - CAM_SPLIT NCAM doubles camp leaves unused hold (D)'s task queue: the ticket word in the
+    // last one, and ahead of it FBA_LR_PROFILE's finish time of the last task of each kind)
+    static_assert(CAM_SPLIT * NCAM <= 490, "camp's tail holds the (D) task queue's words");
+    int* tick = reinterpret_cast<int*>(camp + 511);
+    unsigned long long* tlast = reinterpret_cast<unsigned long long*>(camp + 508);  // [3]
     int* pl = reinterpret_cast<int*>(camp + 512);            // [CHUNK_OBS] chunk-local point or -1
     int* s_pkt = pl + CHUNK_OBS;                             // [<= CT + 1] term offsets of the pair keys
     int* s_term = s_pkt + R_::CT + 1;                        // [<= CT]
@@ -622,6 +632,10 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
         }
     }
     if (t < CHUNK_OBS) pl[t] = (active && p >= 0) ? p - p0 : -1;
+    if (t == LR_THREADS - 1) {  // (D)'s task queue: no ticket taken yet
+        *tick = 0;
+        if (tprof) tlast[0] = tlast[1] = tlast[2] = 0;
+    }
     __syncthreads();
     stamp(1);
     // (B) four lanes per point (g = t & 3): lane g accumulates the point's observations g, g + 4, ..;
@@ -773,14 +787,23 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     }
     __syncthreads();
     stamp(3);
-    // (D) camera entries first (the longest items), then image keys, then pair keys (the plan lists
-    // were staged in LDS before (A)).
+    // (D) a wave-granular task queue over the three kinds of work -- camera entries, image keys, pair
+    // keys (the plan lists were staged in LDS before (A)).  A task is 64 lanes' worth of the items of one
+    // kind; each wave takes tickets from one LDS word (a returning ds_add by one lane, broadcast) and runs
+    // the tasks they decode to until none is left, so no wave idles while another kind still has work.
+    // The kinds only read LDS and write disjoint outputs (camp, ipart, ppart), and an item is computed by
+    // the same instructions whichever wave runs it: the results do not depend on the task order
+    // (lr_order, FBA_LR_ORDER), which only decides what is started first.
     const int nob = o1 - o0, np = p1 - p0;
+    const int lane = t & 63;
     // camera entries: parts 0 .. CAM_SPLIT - 2 sum observation sub-ranges, part CAM_SPLIT - 1 the points'
-    // Schur terms (so no thread runs both loops)
-    if (t < CAM_SPLIT * NCAM) {
+    // Schur terms (so no thread runs both loops); task k: items 64 k .. of the (part, entry) items
+    constexpr int NCT = (CAM_SPLIT * NCAM + 63) / 64;
+    auto cam_task = [&](int k) {
+        const int ci = 64 * k + lane;
+        if (ci >= CAM_SPLIT * NCAM) return;
         constexpr int NPK = CW * (CW + 1) / 2;
-        const int it = t % NCAM, part = t / NCAM;
+        const int it = ci % NCAM, part = ci / NCAM;
         int c1 = 0, c2 = -1;
         if (it < NPK) {
             int rem = it;
@@ -808,14 +831,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
                 s -= u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
             }
         camp[part * NCAM + it] = s;
-    }
-    __syncthreads();
-    if (t < NCAM) {
-        double s = 0.0;
-        for (int part = 0; part < CAM_SPLIT; ++part) s += camp[part * NCAM + t];
-        cpart[(int64_t)c * NCAM + t] = s;
-    }
-    stamp(4);
+    };
     // image keys: one 8-lane group per (key, part) -- part 0 the lower diagonal block and RHS (27
     // values), parts 1 and 2 the two halves of the image-camera block -- each lane accumulating
     // every 8th observation of the key from its own LDS rows (no broadcast reads), then a fixed
@@ -830,9 +846,12 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     constexpr int GL = IKL;
     static_assert(GL == 8 || GL == 4, "image-key lanes per unit");
     constexpr int NV = (IV + GL - 1) / GL * GL, M = NV / GL;  // padded to the GL-lane reduce-scatter
-    {
-        const int nk = ki1 - ki0, nu = 3 * nk, g8 = t & (GL - 1);
-        for (int ub = t / GL; ub < nu; ub += LR_THREADS / GL) {
+    // task k: units (64 / GL) k .. of the 3 nk (key, part) units in part-major order, whole units only
+    const int nk = ki1 - ki0, nu = 3 * nk;
+    constexpr int UPT = 64 / GL;
+    auto img_task = [&](int k) {
+        const int g8 = lane & (GL - 1), ub = UPT * k + lane / GL;
+        if (ub < nu) {
             const int part = ub / nk, K = ki0 + ub % nk;
             const int x0 = s_iko[K - ki0], x1 = s_iko[K - ki0 + 1];
             double v[NV];
@@ -859,9 +878,14 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
                                                           uu[3 * aa + 2] * uu[3 * bb + 2]);
                     double rb0 = 0.0, rb1 = 0.0, rb2 = 0.0;
                     if (pq >= 0) { const double* pp = PP + pq * PPS; rb0 = pp[12]; rb1 = pp[13]; rb2 = pp[14]; }
+                    // (U rb spelled out as the compiler contracts every three-product sum of this loop, u2 r2 +
+                    // (u0 r0 + (u1 r1)): with rb loaded under a condition it has been seen to pick u1 r1 + (u0 r0)
+                    // instead when the code around the loop changed, one ulp apart in a third of the entries)
 #pragma unroll
-                    for (int aa = 0; aa < 6; ++aa)
-                        v[21 + aa] += e[aa] * e[12] + e[6 + aa] * e[13] - (uu[3 * aa] * rb0 + uu[3 * aa + 1] * rb1 + uu[3 * aa + 2] * rb2);
+                    for (int aa = 0; aa < 6; ++aa) {
+                        const double ur = __builtin_fma(uu[3 * aa + 2], rb2, __builtin_fma(uu[3 * aa], rb0, uu[3 * aa + 1] * rb1));
+                        v[21 + aa] += e[aa] * e[12] + e[6 + aa] * e[13] - ur;
+                    }
                 } else {
                     const int q0 = (part - 1) * HALF;
                     double e[12];
@@ -917,16 +941,14 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             for (int j = 0; j < M; ++j)
                 if (q0 + j < nval) out[q0 + j] = h1[j];
         }
-    }
-    if (tprof) {  // FBA_LR_PROFILE: image keys and pair keys timed apart (a barrier the real run does not have)
-        __syncthreads();
-        stamp(6);
-    }
+    };
     // pair keys: one thread per (key, rows 2h, 2h+1) of the pair block, outputs in registers; the term
-    // lists from LDS (staged above) or, for a chunk of one very large point, from HBM
-    auto pair_items = [&](const int* __restrict__ pk, const int* __restrict__ tr, int toff_) {
-        const int n3 = 3 * (kp1 - kp0);
-        for (int it = t; it < n3; it += LR_THREADS) {
+    // lists from LDS (staged above) or, for a chunk of one very large point, from HBM; task k: items
+    // 64 k .. of the 3 (kp1 - kp0) (key, row pair) items (a U-row chunk has no pair keys)
+    const int n3 = 3 * (kp1 - kp0);
+    auto pair_items = [&](int k, const int* __restrict__ pk, const int* __restrict__ tr, int toff_) {
+        const int it = 64 * k + lane;
+        if (it < n3) {
             const int K = kp0 + it / 3, a0 = 2 * (it % 3);
             double acc[12];
 #pragma unroll
@@ -953,10 +975,42 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             for (int q = 0; q < 6; ++q) out[q] = double2{-acc[2 * q], -acc[2 * q + 1]};
         }
     };
-    if (stage_terms) pair_items(s_pkt, s_term, 0);
-    else pair_items(A + plan.pk_t + kp0, A + plan.pk_term + tb0, tb0);
-    __syncthreads();
+    // the queue: the kinds' first tickets in the launch's order (LR_ORDER_*), then tickets until none is left
+    const int nit = (nu + UPT - 1) / UPT, npt = (n3 + 63) / 64;
+    const int ord = lr_order == 0 ? LR_ORDER_DEFAULT : lr_order;
+    int sc, si, sp;
+    if (ord == LR_ORDER_CIP) { sc = 0; si = NCT; sp = NCT + nit; }
+    else if (ord == LR_ORDER_ICP) { si = 0; sc = nit; sp = nit + NCT; }
+    else { si = 0; sp = nit; sc = nit + npt; }  // LR_ORDER_IPC
+    const int ntask = NCT + nit + npt;
+    for (;;) {
+        int tk = 0;
+        if (lane == 0) tk = atomicAdd(tick, 1);
+        tk = __builtin_amdgcn_readfirstlane(tk);
+        if (tk >= ntask) break;
+        int kind;
+        if (tk >= sc && tk < sc + NCT) {
+            kind = 0;
+            cam_task(tk - sc);
+        } else if (tk >= si && tk < si + nit) {
+            kind = 1;
+            img_task(tk - si);
+        } else {
+            kind = 2;
+            if (stage_terms) pair_items(tk - sp, s_pkt, s_term, 0);
+            else pair_items(tk - sp, A + plan.pk_t + kp0, A + plan.pk_term + tb0, tb0);
+        }
+        if (tprof && lane == 0) atomicMax(tlast + kind, (unsigned long long)wall_clock64());
+    }
+    __syncthreads();  // camp complete
+    if (t < NCAM) {
+        double s = 0.0;
+        for (int part = 0; part < CAM_SPLIT; ++part) s += camp[part * NCAM + t];
+        cpart[(int64_t)c * NCAM + t] = s;
+    }
     stamp(5);
+    if (tprof && t == 0)  // FBA_LR_PROFILE: when the last task of each kind finished (0: the chunk had none)
+        for (int q = 0; q < 3; ++q) tprof[(int64_t)blockIdx.x * 8 + (q == 0 ? 4 : 5 + q)] = tlast[q];
 }
 
 // k_red_pairs: S(e1, e2) = the sum of the pair's partials in chunk order; seven pairs per wave, 9 lanes
@@ -1850,8 +1904,8 @@ int launch_accumulate(Ctx& c, bool zeroed) {
     c.d_xy, c.d_img, c.d_cam, c.d_pt, c.d_lp_tie, c.d_ctl, c.d_xfull, c.d_img_tab, c.d_cam_tab, c.d_chunk_obs,    \
         c.d_chunk_pt, c.d_lp_start, c.d_acc, c.acc, c.d_WT, c.d_pt_tab, c.d_ppart, c.d_ipart, c.d_cpart, c.L.u_c, \
         c.set.type, c.cam_tab_stride, em, cm, px, py, c.d_lrprof, (int)nlr, c.d_S, L.ld, c.d_sched + c.sched.zero, \
-        c.d_xoff, c.d_U, c.whiten(), c.d_scal + SCAL_DAMP
-#define ACC(NKV)                                                                                                  \
+        c.d_xoff, c.d_U, c.whiten(), c.d_scal + SCAL_DAMP, c.lr_order
+#define ACC(NKV)                                                                                                 \
     if (nlr > 0 && c.ik_lanes == 4 && !lr_wh)                                                                     \
         k_lin_reduce<NKV, 4, false><<<(unsigned)(nlr + ztail), LR_THREADS, LR<NKV>::LDS, c.stream>>>(LR_ARGS);    \
     else if (nlr > 0 && !lr_wh)                                                                                   \
