@@ -946,7 +946,7 @@ static int create(const fba_problem* p, const fba_settings* s, const fba_options
     }
     FBA_HIP(hipMemset(c->d_scal, 0, sizeof(double) * 16));  // (chol_setup then sets scal[SCAL_SPINS])
     if ((rc = chol_setup(*c)) || (rc = acc_setup(*c))) { destroy(c); return rc; }
-    if (getenv("FBA_LR_PROFILE") && c->n_chunks_lr > 0) FBA_HIP(hipMalloc((void**)&c->d_lrprof, sizeof(uint64_t) * 8 * c->n_chunks_lr));
+    if (getenv("FBA_LR_PROFILE") && c->n_chunks_lr > 0) FBA_HIP(hipMalloc((void**)&c->d_lrprof, sizeof(uint64_t) * LR_PROF * c->n_chunks_lr));
     if (getenv("FBA_PANEL_TRACE") && c->sched.n_waves > 0)
     {
         const size_t nt = std::max<size_t>((size_t)PTRACE_WG * c->sched.n_waves, (size_t)c->sched.flow_n * FTRACE / 8);
@@ -1033,26 +1033,30 @@ static int accumulate_body(Ctx* c) {
     // the camera-side priors behind the reductions' stores of the summed partials, ahead of the pack and the border
     if ((rc = launch_accumulate(*c)) || (rc = launch_gen_reduce(*c)) || (rc = launch_prior_cam(*c))) return rc;
     if (c->d_lrprof) {  // FBA_LR_PROFILE: per-phase averages of k_lin_reduce (us)
-        std::vector<uint64_t> tp(8 * c->n_chunks_lr);
+        std::vector<uint64_t> tp(LR_PROF * c->n_chunks_lr);
         FBA_HIP(hipMemcpyAsync(tp.data(), c->d_lrprof, sizeof(uint64_t) * tp.size(), hipMemcpyDeviceToHost, c->stream));
         FBA_HIP(hipStreamSynchronize(c->stream));
-        // stamps: 0 start, 1 model done, 2 points done, 3 (D) starts, 5 (D) and the camera sum done; 4, 6, 7 the
-        // finish of the last camera, image-key and pair-key task of (D)'s queue (0: the chunk had none)
-        double ph[7] = {0, 0, 0, 0, 0, 0, 0};
+        // stamps (wave 0's): 0 start, 1 model done, 2 points done, 3 couplings done: the queues start, 5 the queues and
+        // the camera sum done; 4, 6, 7 the finish of the last camera (points' part), image-key and pair-key task of (D)'s
+        // queue, 8 of the last early task (camera observation sums; 0: the chunk had none); 9 the early tasks
+        // waves 4-7 had finished at stamp 3, under the point phases
+        double ph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         uint64_t lo = UINT64_MAX, hi = 0;
         const double nch = (double)c->n_chunks_lr;
         for (int64_t ch = 0; ch < c->n_chunks_lr; ++ch) {
-            const uint64_t* q = &tp[8 * ch];
+            const uint64_t* q = &tp[LR_PROF * ch];
             for (int i = 0; i < 3; ++i) ph[i] += (double)(q[i + 1] - q[i]) * 0.01 / nch;
             ph[3] += (double)(q[5] - q[3]) * 0.01 / nch;  // (D)
-            const int last[3] = {4, 6, 7};
-            for (int k = 0; k < 3; ++k) ph[4 + k] += (double)(std::max(q[last[k]], q[3]) - q[3]) * 0.01 / nch;
+            const int last[4] = {4, 6, 7, 8};
+            for (int k = 0; k < 4; ++k) ph[4 + k] += (double)(std::max(q[last[k]], q[3]) - q[3]) * 0.01 / nch;
+            ph[8] += (double)q[9] / nch;
             lo = std::min(lo, q[0]);
             hi = std::max(hi, q[5]);
         }
         fprintf(stderr, "[fba] k_lin_reduce per chunk (us): model %.2f points %.2f couplings %.2f queue %.2f "
-                "(last task done at: camera %.2f image keys %.2f pair keys %.2f; order %d); span %.1f\n", ph[0], ph[1],
-                ph[2], ph[3], ph[4], ph[5], ph[6], c->lr_order, (double)(hi - lo) * 0.01);
+                "(last task done at: early camera %.2f camera %.2f image keys %.2f pair keys %.2f; order %d; "
+                "early tasks done under the point phases %.2f); span %.1f\n", ph[0], ph[1], ph[2], ph[3], ph[7], ph[4],
+                ph[5], ph[6], c->lr_order, ph[8], (double)(hi - lo) * 0.01);
     }
     if (c->sched.split) {
         // subtree split: the top rows' accumulated diagonal (before k_border_rhs writes unit rows), the

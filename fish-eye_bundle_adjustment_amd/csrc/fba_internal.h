@@ -33,6 +33,7 @@ inline double spin_bound_value(long long spins) {
 }
 constexpr int SCAL_DAMP = 7;   // d_scal slot: the Levenberg-Marquardt damping parameter lambda (fba_set_damping; 0: off)
 constexpr int CHUNK_OBS = 256;  // observations per k_lin_reduce / k_lin_point workgroup (chunk)
+constexpr int LR_PROF = 10;     // FBA_LR_PROFILE: 64-bit words per chunk (k_lin_reduce's stamps, fba_capi.cpp's print)
 // tie points per chunk and co-visibility terms per chunk staged in LDS (a single larger point's are
 // read from HBM instead): smaller for nK >= 6, whose wider Jacobian rows leave less of the 160 KiB LDS
 // (k_lin_reduce's LR<NK>::LDS, static_assert there); the host chunking uses the same numbers
@@ -258,7 +259,7 @@ struct Ctx {
     int ik_lanes = 8;                // k_lin_reduce's lanes per image-key unit (4: keys of <= 2 observations)
     int lr_order = 0;                // FBA_LR_ORDER at creation: the order of k_lin_reduce's (D) task queue (0: default)
     double* d_ipart = nullptr;       // [acc.n_ik][27 + 6 cw] image partials: diagonal block, RHS, image-camera
-    uint64_t* d_lrprof = nullptr;    // FBA_LR_PROFILE: k_lin_reduce phase timestamps [n_chunks][8]
+    uint64_t* d_lrprof = nullptr;    // FBA_LR_PROFILE: k_lin_reduce phase timestamps [n_chunks][LR_PROF]
     uint64_t* d_ptrace = nullptr;    // FBA_PANEL_TRACE: k_panel workgroup timestamps [level][PTRACE_WG][8]
     double* d_cpart = nullptr;       // [n_chunks][cw(cw+1)/2 + cw] camera-block partials
     int32_t* d_chunk_obs = nullptr;  // [n_chunks+1] observation range of each chunk

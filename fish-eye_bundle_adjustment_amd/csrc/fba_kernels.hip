@@ -539,7 +539,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     }
     // optional phase timestamps (FBA_LR_PROFILE): 100 MHz wall clock at the phase boundaries
     auto stamp = [&](int i) {
-        if (tprof && threadIdx.x == 0) tprof[(int64_t)blockIdx.x * 8 + i] = wall_clock64();
+        if (tprof && threadIdx.x == 0) tprof[(int64_t)blockIdx.x * LR_PROF + i] = wall_clock64();
     };
     stamp(0);
     constexpr int CW = LY::CW, NJ = LY::NJ, PS = LY::PS;
@@ -556,6 +556,11 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     static_assert(CAM_SPLIT * NCAM <= 490, "camp's tail holds the (D) task queue's words");
     int* tick = reinterpret_cast<int*>(camp + 511);
     unsigned long long* tlast = reinterpret_cast<unsigned long long*>(camp + 508);  // [3]
+    // (and ahead of those the early queue's words: its ticket, the arrival counters of waves 0-3 after (B)
+    // and after (C), the early tasks waves 4-7 have finished, a lost-arrival mark; the finish of its last task)
+    int* qw = reinterpret_cast<int*>(camp + 504);
+    int* etick = qw, *s_bdone = qw + 1, *s_cdone = qw + 2, *s_edone = qw + 3, *s_lost = qw + 4;
+    unsigned long long* tlast_e = reinterpret_cast<unsigned long long*>(camp + 503);
     int* pl = reinterpret_cast<int*>(camp + 512);            // [CHUNK_OBS] chunk-local point or -1
     int* s_pkt = pl + CHUNK_OBS;                             // [<= CT + 1] term offsets of the pair keys
     int* s_term = s_pkt + R_::CT + 1;                        // [<= CT]
@@ -607,6 +612,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     double jr[2][NJ];
     double w0 = 0.0, w1 = 0.0;
     int p = -1;
+    const double sx = sqrt(px), sy = sqrt(py);
     // (A)
     if (active) {
         // (the point's coordinates at xfull[xoff[o]]: one gather level fewer than pt -> lp_tie -> xfull)
@@ -621,23 +627,55 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             double s0, s1;
             whiten_rows<NJ>(wh, o, px, py, jr, w0, w1, s0, s1);
         }
+        // the observation's LDS row, written once: the P^1/2-scaled Je rows and misclosures (what (D)'s image
+        // keys sum), and the raw Jc rows, which (B) reads raw and (D) scales where it reads them (sx Jc, the
+        // same single product)
+        double* er = QE + t * ES;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { er[a] = sx * jr[0][a]; er[6 + a] = sy * jr[1][a]; }
+        er[12] = sx * w0;
+        er[13] = sy * w1;
+#pragma unroll
+        for (int m = 0; m < CW; ++m) { er[14 + m] = jr[0][6 + m]; er[14 + CW + m] = jr[1][6 + m]; }
         if (p >= 0) {
-            double* q = QE + t * ES;  // Jp (2x3) | w (2) | Jc (2xCW), raw
+            double* r = Us + t * US;  // raw Jp (2x3) | w (2) for (B), in the row (C) fills with U afterwards
 #pragma unroll
-            for (int m = 0; m < 3; ++m) { q[m] = jr[0][6 + CW + m]; q[3 + m] = jr[1][6 + CW + m]; }
-            q[6] = w0;
-            q[7] = w1;
-#pragma unroll
-            for (int m = 0; m < CW; ++m) { q[8 + m] = jr[0][6 + m]; q[8 + CW + m] = jr[1][6 + m]; }
+            for (int m = 0; m < 3; ++m) { r[m] = jr[0][6 + CW + m]; r[3 + m] = jr[1][6 + CW + m]; }
+            r[6] = w0;
+            r[7] = w1;
         }
     }
     if (t < CHUNK_OBS) pl[t] = (active && p >= 0) ? p - p0 : -1;
-    if (t == LR_THREADS - 1) {  // (D)'s task queue: no ticket taken yet
+    if (t == LR_THREADS - 1) {  // the task queues: no ticket taken yet, no wave arrived
         *tick = 0;
-        if (tprof) tlast[0] = tlast[1] = tlast[2] = 0;
+        *etick = *s_bdone = *s_cdone = *s_edone = *s_lost = 0;
+        if (tprof) tlast[0] = tlast[1] = tlast[2] = *tlast_e = 0;
     }
     __syncthreads();
     stamp(1);
+    // From here to the camera sum the waves meet at no workgroup barrier.  Waves 0-3 run the point phases
+    // (B) and (C) and count their arrivals after each in LDS (workgroup-scope release / acquire, as the
+    // potrf's counters); waves 4-7 start on the early queue at once -- the camera entries' observation
+    // sums, which read only what (A) stored -- and every wave checks the second counter before its first
+    // task that reads U rows or the point table.  Each wait is for waves 0-3 of this workgroup, which reach
+    // their arrivals unconditionally (outside every per-thread branch) and wait for nothing but each other.
+    // The polls are bounded: a lost arrival would be a bug, reported as NaN camera sums, not a hang.
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    auto arrive = [&](int* cnt) {  // after this wave's LDS stores
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    auto wait_four = [&](int* cnt) {
+        unsigned spins = 0;
+        while (__hip_atomic_load(cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 4) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins >= (1u << 22)) {
+                *s_lost = 1;
+                break;
+            }
+        }
+    };
     // (B) four lanes per point (g = t & 3): lane g accumulates the point's observations g, g + 4, ..;
     // V and b are all-reduced over the four lanes, the camera couplings Wc reduce-scattered (lane g
     // keeps camera columns [CWQ g', CWQ g' + CWQ)), each by two DPP exchange steps in a fixed order;
@@ -652,7 +690,8 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
 #pragma unroll
         for (int q = 0; q < CWP; ++q) Wc[q][0] = Wc[q][1] = Wc[q][2] = 0.0;
         for (int i = a0 + g; i < a1; i += 4) {
-            const double* r = QE + i * ES;
+            const double* r = Us + i * US;          // raw Jp | w
+            const double* rc = QE + i * ES + 14;    // raw Jc
 #pragma unroll
             for (int row = 0; row < 2; ++row) {
                 const double pr = row ? py : px;
@@ -663,7 +702,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
                 V[6] += q0 * wv; V[7] += q1 * wv; V[8] += q2 * wv;
 #pragma unroll
                 for (int q = 0; q < CW; ++q) {
-                    const double jc = r[8 + row * CW + q];
+                    const double jc = rc[row * CW + q];
                     Wc[q][0] += jc * q0; Wc[q][1] += jc * q1; Wc[q][2] += jc * q2;
                 }
             }
@@ -739,7 +778,10 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             }
         }
     }
-    __syncthreads();
+    if (wave < 4) {  // the point table complete (and the raw Jp rows read) before (C)
+        arrive(s_bdone);
+        wait_four(s_bdone);
+    }
     stamp(2);
     // (C)
     const bool urow = A[plan.ck_tm + c] != 0;  // U-row chunk: its pair terms are reduced by k_red_blocks
@@ -776,35 +818,19 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
 #pragma unroll
             for (int m = 0; m < 18; ++m) u[m] = 0.0;
         }
-        const double sx = sqrt(px), sy = sqrt(py);
-        double* E = QE + t * ES;  // own row: the point phase has finished reading it
-#pragma unroll
-        for (int a = 0; a < 6; ++a) { E[a] = sx * jr[0][a]; E[6 + a] = sy * jr[1][a]; }
-        E[12] = sx * w0;
-        E[13] = sy * w1;
-#pragma unroll
-        for (int q = 0; q < CW; ++q) { E[14 + q] = sx * jr[0][6 + q]; E[14 + CW + q] = sy * jr[1][6 + q]; }
     }
-    __syncthreads();
+    if (wave < 4) arrive(s_cdone);  // this wave's U rows stored (the point table was complete before (C))
     stamp(3);
-    // (D) a wave-granular task queue over the three kinds of work -- camera entries, image keys, pair
-    // keys (the plan lists were staged in LDS before (A)).  A task is 64 lanes' worth of the items of one
-    // kind; each wave takes tickets from one LDS word (a returning ds_add by one lane, broadcast) and runs
-    // the tasks they decode to until none is left, so no wave idles while another kind still has work.
-    // The kinds only read LDS and write disjoint outputs (camp, ipart, ppart), and an item is computed by
-    // the same instructions whichever wave runs it: the results do not depend on the task order
-    // (lr_order, FBA_LR_ORDER), which only decides what is started first.
+    if (tprof && t == 0)  // FBA_LR_PROFILE: the early tasks waves 4-7 finished under (B) and (C)
+        tprof[(int64_t)blockIdx.x * LR_PROF + 9] = (uint64_t)__hip_atomic_load(s_edone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const int nob = o1 - o0, np = p1 - p0;
-    const int lane = t & 63;
     // camera entries: parts 0 .. CAM_SPLIT - 2 sum observation sub-ranges, part CAM_SPLIT - 1 the points'
-    // Schur terms (so no thread runs both loops); task k: items 64 k .. of the (part, entry) items
-    constexpr int NCT = (CAM_SPLIT * NCAM + 63) / 64;
-    auto cam_task = [&](int k) {
-        const int ci = 64 * k + lane;
-        if (ci >= CAM_SPLIT * NCAM) return;
+    // Schur terms; the entry (c1, c2) of item it: c2 >= 0 a block entry, c2 < 0 the right-hand side's c1
+    constexpr int NO = CAM_SPLIT - 1;
+    auto cam_entry = [&](int it, int& c1, int& c2) {
         constexpr int NPK = CW * (CW + 1) / 2;
-        const int it = ci % NCAM, part = ci / NCAM;
-        int c1 = 0, c2 = -1;
+        c1 = 0;
+        c2 = -1;
         if (it < NPK) {
             int rem = it;
             while (rem > c1) { rem -= c1 + 1; ++c1; }
@@ -812,25 +838,71 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
         } else {
             c1 = it - NPK;
         }
-        constexpr int NO = CAM_SPLIT - 1;
-        const int l0 = part < NO ? nob * part / NO : 0, l1 = part < NO ? nob * (part + 1) / NO : 0;
+    };
+    // The early queue: the (part < CAM_SPLIT - 1, entry) items, 64 per task, tickets from a word of their
+    // own.  They read the rows (A) stored and nothing else, so waves 4-7 run them while waves 0-3 are in
+    // (B) and (C); those take what is left of them afterwards.  The P^1/2-scaled camera columns are formed
+    // from the raw ones as (C) used to store them (one product each); the sum of the two row products has
+    // the association the compiler gave the plain expression, first product fused: fma(a, s0, b s1)
+    constexpr int NET = (NO * NCAM + 63) / 64;
+    for (;;) {
+        // (a convergent operation at the head of the body: without it the compiler has threaded the lanes other
+        // than 0 from the lane-0 branch at the end of the body past the one below, to a broadcast that then ran
+        // without lane 0 and handed them ticket 0 for ever)
+        __builtin_amdgcn_wave_barrier();
+        int tk = 0;
+        if (lane == 0) tk = atomicAdd(etick, 1);
+        tk = __builtin_amdgcn_readfirstlane(tk);
+        if (tk >= NET) break;
+        const int ci = 64 * tk + lane;
+        if (ci < NO * NCAM) {
+            const int it = ci % NCAM, part = ci / NCAM;
+            int c1, c2;
+            cam_entry(it, c1, c2);
+            const int l0 = nob * part / NO, l1 = nob * (part + 1) / NO;
+            // (the second factor without a branch: the column's address and scale, or the misclosure's, which is
+            // stored scaled -- times 1, exactly)
+            const int o0_ = (c2 >= 0) ? 14 + c2 : 12, o1_ = (c2 >= 0) ? 14 + CW + c2 : 13;
+            const double m0 = (c2 >= 0) ? sx : 1.0, m1 = (c2 >= 0) ? sy : 1.0;
+            double s = 0.0;
+#pragma unroll 4
+            for (int l = l0; l < l1; ++l) {
+                const double* r = QE + l * ES;
+                const double s0 = m0 * r[o0_], s1 = m1 * r[o1_];
+                const double a = sx * r[14 + c1], b = sy * r[14 + CW + c1];
+                s += __builtin_fma(a, s0, b * s1);
+            }
+            camp[part * NCAM + it] = s;
+        }
+        if (tprof && lane == 0) {
+            if (wave >= 4) __hip_atomic_fetch_add(s_edone, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            atomicMax(tlast_e, (unsigned long long)wall_clock64());
+        }
+    }
+    wait_four(s_cdone);  // every U row and the point table, before the first task that reads them
+    // (D) a wave-granular task queue over the three kinds of work -- camera entries (the points' part), image
+    // keys, pair keys (the plan lists were staged in LDS before (A)).  A task is 64 lanes' worth of the items
+    // of one kind; each wave takes tickets from one LDS word (a returning ds_add by one lane, broadcast) and
+    // runs the tasks they decode to until none is left, so no wave idles while another kind still has work.
+    // The kinds only read LDS and write disjoint outputs (camp, ipart, ppart), and an item is computed by
+    // the same instructions whichever wave runs it: the results do not depend on the task order
+    // (lr_order, FBA_LR_ORDER), which only decides what is started first.
+    // camera entries, the points' Schur terms: task k: entries 64 k ..
+    constexpr int NCT = (NCAM + 63) / 64;
+    auto cam_task = [&](int k) {
+        const int it = 64 * k + lane;
+        if (it >= NCAM) return;
+        int c1, c2;
+        cam_entry(it, c1, c2);
         double s = 0.0;
 #pragma unroll 4
-        for (int l = l0; l < l1; ++l) {
-            const double* r = QE + l * ES;
-            const double s0 = (c2 >= 0) ? r[14 + c2] : r[12];
-            const double s1 = (c2 >= 0) ? r[14 + CW + c2] : r[13];
-            s += r[14 + c1] * s0 + r[14 + CW + c1] * s1;
+        for (int q = 0; q < np; ++q) {
+            const double* pp = PP + q * PPS;
+            const double* u1 = pp + 15 + 3 * c1;
+            const double* u2 = (c2 >= 0) ? pp + 15 + 3 * c2 : pp + 12;
+            s -= u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
         }
-        if (part == CAM_SPLIT - 1)  // the points' Schur terms
-#pragma unroll 4
-            for (int q = 0; q < np; ++q) {
-                const double* pp = PP + q * PPS;
-                const double* u1 = pp + 15 + 3 * c1;
-                const double* u2 = (c2 >= 0) ? pp + 15 + 3 * c2 : pp + 12;
-                s -= u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
-            }
-        camp[part * NCAM + it] = s;
+        camp[NO * NCAM + it] = s;
     };
     // image keys: one 8-lane group per (key, part) -- part 0 the lower diagonal block and RHS (27
     // values), parts 1 and 2 the two halves of the image-camera block -- each lane accumulating
@@ -894,7 +966,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
 #pragma unroll
                     for (int q = 0; q < HALF; ++q) {
                         if (q0 + q >= CW) continue;
-                        const double fx = E[14 + q0 + q], fy = E[14 + CW + q0 + q];
+                        const double fx = sx * E[14 + q0 + q], fy = sy * E[14 + CW + q0 + q];  // (LDS holds Jc raw)
                         double c0 = 0.0, c1 = 0.0, c2 = 0.0;
                         if (pq >= 0) {
                             const double* pp = PP + pq * PPS + 15 + 3 * (q0 + q);
@@ -984,6 +1056,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     else { si = 0; sp = nit; sc = nit + npt; }  // LR_ORDER_IPC
     const int ntask = NCT + nit + npt;
     for (;;) {
+        __builtin_amdgcn_wave_barrier();  // (as in the early queue's loop)
         int tk = 0;
         if (lane == 0) tk = atomicAdd(tick, 1);
         tk = __builtin_amdgcn_readfirstlane(tk);
@@ -1006,11 +1079,14 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
     if (t < NCAM) {
         double s = 0.0;
         for (int part = 0; part < CAM_SPLIT; ++part) s += camp[part * NCAM + t];
+        if (*s_lost) s = __builtin_nan("");  // an arrival poll ran out
         cpart[(int64_t)c * NCAM + t] = s;
     }
     stamp(5);
-    if (tprof && t == 0)  // FBA_LR_PROFILE: when the last task of each kind finished (0: the chunk had none)
-        for (int q = 0; q < 3; ++q) tprof[(int64_t)blockIdx.x * 8 + (q == 0 ? 4 : 5 + q)] = tlast[q];
+    if (tprof && t == 0) {  // FBA_LR_PROFILE: when the last task of each kind finished (0: the chunk had none)
+        for (int q = 0; q < 3; ++q) tprof[(int64_t)blockIdx.x * LR_PROF + (q == 0 ? 4 : 5 + q)] = tlast[q];
+        tprof[(int64_t)blockIdx.x * LR_PROF + 8] = *tlast_e;
+    }
 }
 
 // k_red_pairs: S(e1, e2) = the sum of the pair's partials in chunk order; seven pairs per wave, 9 lanes
