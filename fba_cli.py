@@ -5,6 +5,9 @@
                                                --reliability also writes the .rel table (report.write_rel)
     ... main <folder> ... --ellipsoids         also writes the .ell table (report.write_ell): every tie point's
                                                sigma X Y Z, 1-sigma error ellipsoid and horizontal error ellipse
+    ... main <folder> ... --intersect          the tie points' starting values by forward intersection of their image
+                                               rays instead of the .cnt coordinates; also writes the .fwd table
+                                               (report.write_fwd)
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
     ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
                                                of sigma (default: the 95 %-efficiency constants, huber 1.345,

@@ -111,6 +111,12 @@ def parse_ellipsoids(args):
     return [a for a in args if a != "--ellipsoids"], "--ellipsoids" in args
 
 
+def parse_intersect(args):
+    """--intersect anywhere in args -> (args without it, True / False): the tie points' starting values by forward
+    intersection of their image rays (`main` only; writes the .fwd table)"""
+    return [a for a in args if a != "--intersect"], "--intersect" in args
+
+
 def parse_robust(args):
     """--robust huber[:k] | cauchy[:k] (also --robust=...) anywhere in args -> (args without it, loss or None,
     k or None).  ValueError for a missing or unknown loss, or a k that is not a positive number."""
@@ -142,19 +148,21 @@ def parse_robust(args):
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
     anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors', --lm parse_lm's)"""
-    args = parse_ellipsoids(parse_lm(parse_priors(parse_robust(args)[0])[0])[0])[0]
+    args = parse_intersect(parse_ellipsoids(parse_lm(parse_priors(parse_robust(args)[0])[0])[0])[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
          "batch <folder>... [--robust LOSS[:k]] [--priors] [--lm[=lambda0]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
          "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
          "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
          "<std> per row) as prior observations of unknowns;\n      writes the .prr table\n  --lm[=lambda0]  "
          "Levenberg-Marquardt trials with step control (first lambda 1e-3), then undamped passes, in place of\n"
          "      the Gauss-Newton loop: for coarse starting values; writes the .lm table\n  --ellipsoids  (main) every tie "
-         "point's full 3 x 3 covariance and 1-sigma error ellipsoid; writes the .ell table")
+         "point's full 3 x 3 covariance and 1-sigma error ellipsoid; writes the .ell table\n  --intersect  (main) the tie "
+         "points' starting values by forward intersection of their image rays instead of the .cnt\n      coordinates; "
+         "writes the .fwd table")
 
 
 def cli(argv=None):
@@ -166,6 +174,7 @@ def cli(argv=None):
         argv, lm = parse_lm(argv)
         argv, robust, robust_k = parse_robust(argv)
         argv, ellipsoids = parse_ellipsoids(argv)
+        argv, intersect = parse_intersect(argv)
     except ValueError as e:
         print(f"Error: {e}")
         print(USAGE)
@@ -174,7 +183,8 @@ def cli(argv=None):
         from .bundle import main
         folder, plot, reliability = parse_main(argv[1:])
         return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors),
-                    **_lm_kw(lm), **({"ellipsoids": True} if ellipsoids else {}))
+                    **_lm_kw(lm), **({"ellipsoids": True} if ellipsoids else {}),
+                    **({"intersect": True} if intersect else {}))
     if len(argv) >= 2 and argv[0] == "batch":
         done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors), **({"lm": lm} if lm else {}))
         return 1 if any(e for _, e in done) else 0

@@ -97,6 +97,11 @@ class Adjustment:
     cx_tie: np.ndarray = None      # (n_tie, 3, 3), full symmetric
     ell_axes: np.ndarray = None    # (n_tie, 3)
     ell_dirs: np.ndarray = None    # (n_tie, 3, 3)
+    # forward intersection of the starting values (intersect=True), TIE order: the intersected X Y Z, per point
+    # [rays used, lambda_min / lambda_max, RMS px linear, RMS px refined], and FBA_ISECT_* (capi.ISECT_STATUS)
+    isect_xyz: np.ndarray = None      # (n_tie, 3)
+    isect_quality: np.ndarray = None  # (n_tie, 4)
+    isect_status: np.ndarray = None   # (n_tie)
 
 
 def _priors_of(data, priors):
@@ -122,7 +127,8 @@ def prior_statistics(sigma02, cx_diag, index, sigma, v):
 
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
-           reliability=False, priors=None, method="gn", lm_options=None, point_precision=False) -> Adjustment:
+           reliability=False, priors=None, method="gn", lm_options=None, point_precision=False,
+           intersect=False) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -149,7 +155,13 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     point_precision (no reference counterpart: main.m:460-482 keeps the diagonal of Cx): fba_postfit_outputs in
     place of fba_covariance / fba_reliability -- the same outputs (reliability's too when that is asked for), plus
     every tie point's full 3 x 3 covariance block and 1-sigma error ellipsoid: Adjustment.cx_tie, ell_axes,
-    ell_dirs."""
+    ell_dirs.
+
+    intersect (no reference counterpart: Buildxhat.m:107-134 copies the .cnt coordinates): before the loop, "gn" or
+    "lm", every tie point is intersected from its image rays at the starting exterior and interior orientation
+    (fba_intersect with write_xhat: linear line intersection, then point-only Gauss-Newton) and replaces its .cnt
+    starting value; a point with fewer than two usable rays or too flat an intersection keeps it.
+    Adjustment.isect_xyz, isect_quality and isect_status carry the result."""
     if method not in ("gn", "lm"):
         raise ValueError(f"adjust: unknown method {method!r} (\"gn\" or \"lm\")")
     t0 = time.perf_counter()
@@ -159,6 +171,10 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         if weights is not None:
             ctx.set_weights(weights)
         lmh = None
+        ikw = {}
+        if intersect:
+            ix, iq, ist, _ = ctx.intersect(write_xhat=True)
+            ikw = dict(isect_xyz=ix, isect_quality=iq, isect_status=ist)
         if method == "lm":
             nt, npol, lmh = ctx.adjust_lm(lm_options)
             it, hist = nt + npol, lmh[:, 2].copy()
@@ -195,7 +211,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk)
+                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk, **ikw)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -217,11 +233,13 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_lm(os.path.join(folder, name + ".lm"), res.lm_history)
     if getattr(res, "ell_axes", None) is not None:
         report.write_ell(os.path.join(folder, name + ".ell"), data, res)
+    if getattr(res, "isect_status", None) is not None:
+        report.write_fwd(os.path.join(folder, name + ".fwd"), data, res)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False, method="gn", lm_options=None, ellipsoids=False) -> int:
+         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
@@ -229,7 +247,9 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
     table as prior observations of unknowns (io.read_pri; without the file main returns 1); the .prr table
     (report.write_prr) is written too.  method="lm" (lm_options: adjust()'s): the damped loop of fba_adjust_lm
     in place of the Gauss-Newton loop; the .lm table (report.write_lm) is written too.  ellipsoids=True:
-    adjust()'s point_precision; the .ell table (report.write_ell) is written too."""
+    adjust()'s point_precision; the .ell table (report.write_ell) is written too.  intersect=True: adjust()'s
+    intersect -- the tie points' starting values from their image rays instead of the .cnt file; the .fwd table
+    (report.write_fwd) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
@@ -237,6 +257,7 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
         res = adjust(data, device=device, reliability=reliability, robust=robust, robust_k=robust_k,
                      **({"priors": True} if priors else {}),
                      **({"point_precision": True} if ellipsoids else {}),
+                     **({"intersect": True} if intersect else {}),
                      **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:

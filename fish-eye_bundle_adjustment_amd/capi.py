@@ -19,6 +19,8 @@ LOSSES = ("none", "huber", "cauchy")  # FBA_LOSS_*
 # the usual 95 %-efficiency tuning constants (in units of sigma)
 LOSS_K = {"huber": 1.345, "cauchy": 2.385}
 NK_MAX = 8
+RAY_STATUS = ("ok", "domain")                    # FBA_RAY_*
+ISECT_STATUS = ("ok", "few", "weak", "refine")   # FBA_ISECT_*
 
 # every symbol include/fba.h declares
 EXPORTS = (
@@ -31,6 +33,7 @@ EXPORTS = (
     "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
     "fba_set_damping", "fba_cost", "fba_adjust_lm",
     "fba_postfit_outputs",
+    "fba_unproject_host", "fba_image_rays", "fba_intersect",
 )
 # ... but for the host-only helpers whose names carry a digit (tests/test_damping_host.py reads the header's
 # declarations with a letters-only pattern and compares them with EXPORTS)
@@ -77,6 +80,16 @@ class LMOptions(C.Structure):
 
     def __init__(self, lambda0=1e-3, up=10.0, down=10.0, lambda_min=1e-12, lambda_max=1e8, ftol=1e-9):
         super().__init__(lambda0, up, down, lambda_min, lambda_max, ftol)
+
+
+class IntersectOptions(C.Structure):
+    """fba_intersect_options; the defaults are the library's (a NULL pointer)"""
+    _fields_ = [("refine_iters", C.c_int32), ("write_xhat", C.c_int32), ("min_ratio", C.c_double),
+                ("refine_tol", C.c_double)]
+
+    def __init__(self, refine_iters=10, write_xhat=False, min_ratio=0.5 * (1.0 - np.cos(np.pi / 180.0)),
+                 refine_tol=1e-10):
+        super().__init__(int(refine_iters), int(bool(write_xhat)), float(min_ratio), float(refine_tol))
 
 
 def pack_priors(priors):
@@ -144,6 +157,9 @@ def _load():
         "fba_adjust_lm": ([P, P, P, P, P], C.c_int),
         "fba_postfit_outputs": ([P, D, P], C.c_int),
         "fba_eig3_host": ([C.c_int64, P, P], C.c_int),
+        "fba_unproject_host": ([I, I, C.c_int64, P, P, P, P], C.c_int),
+        "fba_image_rays": ([P, P, P], C.c_int),
+        "fba_intersect": ([P, P, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -444,6 +460,29 @@ class Context:
         check(lib.fba_get_priors(self.h, None, ptr(resid), C.byref(vtpv)))
         return resid[:n], vtpv.value
 
+    def image_rays(self):
+        """fba_image_rays: (ray, status) -- per PHO row the projection centre and the unit direction of the
+        measurement's image ray in the object frame, (n_pts, 6), and FBA_RAY_* (n_pts), at the device xhat;
+        other ranks' observations are 0."""
+        n = self.packed.n_pts
+        ray, st = np.zeros((max(n, 1), 6)), np.zeros(max(n, 1), dtype=np.int32)
+        check(lib.fba_image_rays(self.h, ptr(ray), ptr(st)))
+        return ray[:n], st[:n]
+
+    def intersect(self, refine_iters=10, write_xhat=False, min_ratio=None, refine_tol=1e-10):
+        """fba_intersect: (xyz, quality, status, n_not_ok) -- every tie point intersected from its image rays at the
+        device xhat, TIE order: xyz (n_tie, 3); quality (n_tie, 4): rays used, lambda_min / lambda_max of the
+        intersection's normal matrix, RMS reprojection residual (px) of the linear and of the refined solution;
+        status (n_tie) FBA_ISECT_* (capi.ISECT_STATUS); the number of points not OK.  write_xhat: the OK and REFINE
+        points replace their entries of the device xhat.  Other ranks' tie points are 0."""
+        nt = self.packed.n_tie
+        op = IntersectOptions(refine_iters, write_xhat, refine_tol=refine_tol) if min_ratio is None else \
+            IntersectOptions(refine_iters, write_xhat, min_ratio, refine_tol)
+        xyz, q, st = np.zeros((max(nt, 1), 3)), np.zeros((max(nt, 1), 4)), np.zeros(max(nt, 1), dtype=np.int32)
+        bad = C.c_int64()
+        check(lib.fba_intersect(self.h, C.byref(op), ptr(xyz), ptr(q), ptr(st), C.byref(bad)))
+        return xyz[:nt], q[:nt], st[:nt], bad.value
+
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""
         check(lib.fba_set_spin_bound(self.h, int(spins)))
@@ -473,6 +512,18 @@ def eig3_host(blocks):
     out = np.zeros((max(len(b), 1), 12))
     check(lib.fba_eig3_host(len(b), ptr(b) if len(b) else None, ptr(out)))
     return out[: len(b)]
+
+
+def unproject_host(typ, xy, camtab):
+    """fba_unproject_host: the device's inverse projection model (csrc/fba_ray.h) run on the CPU, no GPU needed.
+    typ: a name of TYPES or the FBA_TYPE_* number; xy (n, 2) pixels; camtab: xp yp c ydir P1 P2 K1..Knk ->
+    (out (n, 5): xu yu and the unit direction in the camera frame, status (n) FBA_RAY_*)."""
+    t = TYPES.index(typ) if isinstance(typ, str) else int(typ)
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    ct = np.ascontiguousarray(camtab, dtype=np.float64).reshape(-1)
+    out, st = np.zeros((max(len(xy), 1), 5)), np.zeros(max(len(xy), 1), dtype=np.int32)
+    check(lib.fba_unproject_host(t, ct.size - 6, len(xy), ptr(xy) if len(xy) else None, ptr(ct), ptr(out), ptr(st)))
+    return out[: len(xy)], st[: len(xy)]
 
 
 def tie_blocks(cx_tie):

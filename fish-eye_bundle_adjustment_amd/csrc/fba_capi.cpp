@@ -20,6 +20,7 @@
 
 #include "fba_internal.h"
 #include "fba_eig3.h"
+#include "fba_ray.h"
 
 namespace fba {
 
@@ -2042,6 +2043,120 @@ int fba_postfit_outputs(fba_ctx* ctx, double sigma02, const fba_postfit* out) {
 int fba_eig3_host(int64_t n, const double* blk, double* ell) {
     if (n < 0 || (n > 0 && (!blk || !ell))) { set_error("fba_eig3_host: NULL argument"); return FBA_ERR_ARG; }
     for (int64_t i = 0; i < n; ++i) eig3_block(blk + 6 * i, ell + 12 * i);
+    return FBA_OK;
+}
+
+// ---- forward intersection (no reference counterpart; kernels in fba_intersect.hip) ----
+int fba_unproject_host(int32_t type, int32_t nk, int64_t n, const double* xy, const double* camtab, double* out,
+                       int32_t* status) {
+    if (type < FBA_TYPE_FISHEYE || type > FBA_TYPE_STEREOGRAPHIC) { set_error("fba_unproject_host: invalid type"); return FBA_ERR_TYPE; }
+    if (nk < 1 || nk > FBA_NK_MAX || n < 0 || !camtab || (n > 0 && !xy)) {
+        set_error("fba_unproject_host: nk in 1..FBA_NK_MAX, n >= 0, xy and camtab not NULL");
+        return FBA_ERR_ARG;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        double v[5];
+        const int st = ray_unproject<0>(xy[2 * i], xy[2 * i + 1], camtab[0], camtab[1], camtab[2], camtab[3], camtab[4],
+                                        camtab[5], camtab + 6, nk, type, v[0], v[1], v[2], v[3], v[4]);
+        if (out) std::copy(v, v + 5, out + 5 * i);
+        if (status) status[i] = st;
+    }
+    return FBA_OK;
+}
+
+namespace fba {
+// the rays of this rank's observations at d_xfull into workspace (local order): ray [6 n_obs], rst [n_obs], xu [2 n_obs]
+static int rays_to_ws(Ctx* c, double** d_ray, int32_t** d_rst, double** d_xu) {
+    const size_t n = (size_t)std::max<int64_t>(c->n_obs, 1);
+    int rc;
+    if ((rc = ws_get(*c, 80, sizeof(double) * 6 * n, (void**)d_ray)) || (rc = ws_get(*c, 81, sizeof(int32_t) * n, (void**)d_rst)) ||
+        (rc = ws_get(*c, 82, sizeof(double) * 2 * n, (void**)d_xu)))
+        return rc;
+    // the image / camera tables at d_xfull: functions of xhat alone, so between fba_accumulate and fba_solve_update
+    // they are rewritten with the values they hold (launch_cost's argument)
+    if ((rc = launch_params(*c)) || (rc = launch_rays(*c, *d_ray, *d_rst, *d_xu))) return rc;
+    return FBA_OK;
+}
+}  // namespace fba
+
+int fba_image_rays(fba_ctx* ctx, double* ray, int32_t* status) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_image_rays: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_image_rays between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    double *d_ray = nullptr, *d_xu = nullptr;
+    int32_t* d_rst = nullptr;
+    int rc;
+    if ((rc = rays_to_ws(c, &d_ray, &d_rst, &d_xu))) return rc;
+    const int64_t n = c->n_obs;
+    std::vector<double> hr(6 * (size_t)n);
+    std::vector<int32_t> hs((size_t)n);
+    if (n > 0) {
+        FBA_HIP(hipMemcpyAsync(hr.data(), d_ray, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, c->stream));
+        FBA_HIP(hipMemcpyAsync(hs.data(), d_rst, sizeof(int32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    if (ray) std::fill(ray, ray + 6 * c->n_pts, 0.0);
+    if (status) std::fill(status, status + c->n_pts, 0);
+    for (int64_t o = 0; o < n; ++o) {  // local order -> PHO order; another rank's rows stay 0
+        const int64_t i = c->obs_pho[o];
+        if (ray) std::copy(hr.begin() + 6 * o, hr.begin() + 6 * o + 6, ray + 6 * i);
+        if (status) status[i] = hs[o];
+    }
+    return FBA_OK;
+}
+
+int fba_intersect(fba_ctx* ctx, const fba_intersect_options* o, double* xyz, double* quality, int32_t* status,
+                  int64_t* n_not_ok) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_intersect: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_intersect between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const fba_intersect_options def{10, 0, 0.5 * (1.0 - std::cos(std::acos(-1.0) / 180.0)), 1e-10};
+    const fba_intersect_options& op = o ? *o : def;
+    if (op.refine_iters < 0 || !std::isfinite(op.min_ratio) || op.min_ratio < 0.0 || !std::isfinite(op.refine_tol) ||
+        op.refine_tol < 0.0) {
+        set_error("fba_intersect: refine_iters >= 0, min_ratio and refine_tol finite and >= 0");
+        return FBA_ERR_ARG;
+    }
+    const size_t nt = (size_t)std::max<int32_t>(c->L.n_tie, 1);
+    double *d_ray = nullptr, *d_xu = nullptr, *d_out = nullptr;
+    int32_t *d_rst = nullptr, *d_st = nullptr;
+    int rc;
+    if ((rc = ws_get(*c, 83, sizeof(double) * 7 * nt, (void**)&d_out)) || (rc = ws_get(*c, 84, sizeof(int32_t) * nt, (void**)&d_st)))
+        return rc;
+    // another rank's tie points stay 0 (the ranks' outputs sum to the whole)
+    FBA_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 7 * nt, c->stream));
+    FBA_HIP(hipMemsetAsync(d_st, 0, sizeof(int32_t) * nt, c->stream));
+    hipEvent_t e0 = c->ev[0], e1 = c->ev[1];
+    if (c->timing) (void)hipEventRecord(e0, c->stream);
+    if ((rc = rays_to_ws(c, &d_ray, &d_rst, &d_xu)) ||
+        (rc = launch_intersect(*c, d_ray, d_rst, d_xu, op.refine_iters, op.min_ratio, op.refine_tol, op.write_xhat != 0, d_out,
+                               d_out + 3 * nt, d_st)))
+        return rc;
+    if (c->timing) (void)hipEventRecord(e1, c->stream);
+    if (op.write_xhat) {  // as fba_set_xhat: neither the linearisation nor the factor belongs to the new xhat
+        c->have_lin = false;
+        c->have_delta = false;
+        c->have_factor = false;
+    }
+    const int64_t n_tie = c->L.n_tie;
+    std::vector<int32_t> hs;
+    if (n_tie > 0) {
+        if (xyz) FBA_HIP(hipMemcpyAsync(xyz, d_out, sizeof(double) * 3 * n_tie, hipMemcpyDeviceToHost, c->stream));
+        if (quality) FBA_HIP(hipMemcpyAsync(quality, d_out + 3 * nt, sizeof(double) * 4 * n_tie, hipMemcpyDeviceToHost, c->stream));
+        if (status || n_not_ok) {
+            hs.resize((size_t)n_tie);
+            FBA_HIP(hipMemcpyAsync(hs.data(), d_st, sizeof(int32_t) * n_tie, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    if (status) std::copy(hs.begin(), hs.end(), status);
+    if (n_not_ok) *n_not_ok = (int64_t)std::count_if(hs.begin(), hs.end(), [](int32_t s) { return s != FBA_ISECT_OK; });
+    if (c->timing) {
+        float ms = 0.f;
+        FBA_HIP(hipEventElapsedTime(&ms, e0, e1));
+        std::fill(c->last_ms, c->last_ms + 8, 0.0);
+        c->last_ms[7] = ms;
+    }
     return FBA_OK;
 }
 

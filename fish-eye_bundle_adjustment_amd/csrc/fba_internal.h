@@ -464,6 +464,13 @@ int launch_gen_cov_blk(Ctx& c, const double* Z, const double* Wz, int nz, double
 int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot, const int32_t* d_icam,
                    int n_iblk, double* d_q, double* d_red, double* d_wst, double sigma02, double* d_blk, double* d_ell);
 int launch_dense_awg(Ctx& c, double* dA, double* dG, const int64_t* d_map, int64_t n_rows, int64_t u_ref);
+// forward intersection (fba_intersect.hip), after launch_params at d_xfull.  launch_rays: per local observation
+// ray [6] (C, d in the object frame), rst FBA_RAY_*, xu [2] the corrected image coordinates.  launch_intersect: per
+// local tie point from those, into xyz [3 n_tie] / qual [4 n_tie] / st [n_tie] (TIE order; the caller zeroes them);
+// write: OK / REFINE points also into d_xfull's tie entries
+int launch_rays(Ctx& c, double* ray, int32_t* rst, double* xu);
+int launch_intersect(Ctx& c, const double* ray, const int32_t* rst, const double* xu, int refine_iters, double min_ratio,
+                     double refine_tol, bool write, double* xyz, double* qual, int32_t* st);
 int border_solve_selftest(int device, const double* gram, double* coef);  // fba_test_border_solve
 
 }  // namespace fba

@@ -432,6 +432,50 @@ def read_ell(path):
     return names, v[:, 0:3], v[:, 3:6], v[:, 6:15].reshape(-1, 3, 3), v[:, 15:18]
 
 
+FWD_STATUS = ("OK", "FEW", "WEAK", "REFINE")  # FBA_ISECT_*
+
+
+def write_fwd(path, data, res):
+    """The forward-intersection table <Output_Filename stem>.fwd (no reference counterpart: the reference takes the
+    object points' starting values from the .cnt file; .int is the interior-orientation file, hence .fwd),
+    tab-delimited in write_ell's style, one row per tie point in TIE order: targetID; rays used; the intersected
+    X Y Z; its shift from the .cnt value; lambda_min / lambda_max of the intersection's normal matrix ((1 - |cos a|)
+    / 2 for two rays meeting at the angle a); the RMS reprojection residual in pixels of the linear and of the
+    refined solution; and, where the status is not OK, * and the status word -- FEW (fewer than 2 usable rays) and
+    WEAK (ratio below the bound): the point kept its .cnt value; REFINE: the linear solution was kept."""
+    if getattr(res, "isect_xyz", None) is None or getattr(res, "isect_quality", None) is None or \
+            getattr(res, "isect_status", None) is None:
+        raise ValueError("write_fwd: the adjustment carries no intersection (adjust(..., intersect=True))")
+    xyz = np.asarray(res.isect_xyz, dtype=np.float64).reshape(-1, 3)
+    q = np.asarray(res.isect_quality, dtype=np.float64).reshape(-1, 4)
+    st = np.asarray(res.isect_status).reshape(-1)
+    if not (len(xyz) == len(q) == len(st) == len(data.TIE)):
+        raise ValueError("write_fwd: one intersection per tie point expected")
+    with open(path, "w") as fh:
+        for t, name in enumerate(data.TIE):
+            x0 = np.asarray(data.CNT[name], dtype=np.float64)
+            flag = [] if st[t] == 0 else ["*", FWD_STATUS[int(st[t])]]
+            fh.write("\t".join([name, str(int(q[t, 0]))] + [_cell(v) for v in (*xyz[t], *(xyz[t] - x0), *q[t, 1:])] + flag)
+                     + "\n")
+
+
+def read_fwd(path):
+    """write_fwd's table back: (targetIDs, rays (n), xyz (n, 3), shift (n, 3), quality (n, 3): ratio, RMS linear,
+    RMS final; status words (n), "OK" where the row carries no flag)"""
+    names, rays, vals, words = [], [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if len(c) not in (11, 13) or (len(c) == 13 and c[11] != "*"):
+                raise ValueError(f"read_fwd: {path}: expected 11 tab-separated columns, or 13 with the flag, got {len(c)}")
+            names.append(c[0])
+            rays.append(int(c[1]))
+            vals.append([float(x) for x in c[2:11]])
+            words.append(c[12] if len(c) == 13 else "OK")
+    v = np.array(vals, dtype=np.float64).reshape(-1, 9)
+    return names, np.array(rays, dtype=np.int64), v[:, 0:3], v[:, 3:6], v[:, 6:9], words
+
+
 def read_prr(path):
     """write_prr's table back: (names, values (n, 6): prior, std, adjusted, v, r, w -- NaN for an empty cell --,
     flagged (n) bool)"""

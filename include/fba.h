@@ -385,6 +385,71 @@ int fba_cost(fba_ctx* ctx, double* cost /*[3]: total, image part, prior part*/);
 int fba_adjust_lm(fba_ctx* ctx, const fba_lm_options* o, int32_t* trials, int32_t* polish,
                   double* hist /*[4*Iteration_Cap]: lambda, cost after, deltasum, accepted (1/0)*/);
 
+/* Forward intersection: starting values of the object points from the measured image rays (no reference
+ * counterpart: Buildxhat.m:107-134 copies the .cnt coordinates of the .tie targets, and main.m has no routine that
+ * derives them from the measurements).
+ *
+ * The image ray of a measurement is closed-form in this model, because BuildAwG.m:168-187 evaluates the distortion at
+ * the MEASURED coordinates: xb = x - xp, yb = y - yp, dr = sum K_j r^2j, decx / decy from P1, P2, and the model's
+ * condition w = 0 reads xu = xb - dr xb - decx = -c s U, yu = yb - dr yb - decy = -c ydir s V with s = g(t) / R,
+ * t = atan(R / W).  So rho = hypot(xu, yu) = c |g(t)|, t = ginv(rho / c) per Type -- q (fisheye), atan q (pinhole),
+ * 2 asin(q / 2) (equisolid), asin q (orthographic), 2 atan(q / 2) (stereographic) -- and the unit direction in the
+ * camera frame is (-sin t xu / rho, -ydir sin t yu / rho, cos t); rho = 0 gives the axis (0, 0, 1).  The ray is a LINE
+ * through the projection centre: W > 0 and W < 0 give the same line with the direction reversed, and nothing here
+ * depends on that sign.
+ *
+ * fba_unproject_host (no reference counterpart; host only, no GPU): the device's inverse model (csrc/fba_ray.h) run on
+ *   the CPU.  xy [2 n] pixels; camtab [6 + nk]: xp yp c ydir P1 P2 K1..Knk, one camera for all n; out [5 n] per
+ *   measurement xu yu and the direction; status [n] FBA_RAY_*.  An out-of-range q (orthographic |q| > 1, equisolid
+ *   |q| > 2) or any non-finite input gives FBA_RAY_DOMAIN, xu yu as computed and a zero direction.  out or status may
+ *   be NULL.
+ * fba_image_rays (no reference counterpart): the rays of every image measurement, tie and control alike, at the device
+ *   xhat: ray [6 n_pts] per PHO row the projection centre C (the image's Xc Yc Zc, bit for bit xhat's) and the unit
+ *   direction M' d in the object frame; status [n_pts] FBA_RAY_*.  With world > 1 a rank fills its own observations
+ *   and writes 0 elsewhere (the ranks' outputs sum to the whole; this is why OK is 0).
+ * fba_intersect (no reference counterpart): per tie point, from its rays with status OK (n of them),
+ *   (a) the linear solution of sum (I - d d')(X - C) = 0 -- the point closest to all its lines, independent of the
+ *       directions' signs -- with the origin at the first ray's centre, by the symmetric adjugate; lambda_min /
+ *       lambda_max of A = sum (I - d d') (csrc/fba_eig3.h) measures the intersection geometry: for two rays meeting
+ *       at the angle a it is (1 - |cos a|) / 2;
+ *   (b) up to refine_iters point-only Gauss-Newton passes X <- X - V^-1 b, V = Jp'PJp, b = Jp'Pw of the forward
+ *       model's tie columns with P = diag(1 / Meas_std^2, 1 / Meas_std_y^2) (no user weights, no loss, no priors, no
+ *       damping: contexts that carry them give the same result), stopped when |dX|_inf <= refine_tol x the mean
+ *       distance of X (before the pass) to the rays' centres;
+ *   (c) the RMS reprojection residual sqrt(sum (wx^2 + wy^2) / n) in pixels through the forward model, at the linear
+ *       and at the final solution.
+ *   status per point: FBA_ISECT_OK; FBA_ISECT_FEW fewer than 2 usable rays; FBA_ISECT_WEAK the ratio below min_ratio;
+ *   FBA_ISECT_REFINE the refinement went non-finite or raised the RMS (by more than 1e-9 px), the linear solution is
+ *   returned.  A point intersected on the wrong half-line (a camera looking away from it) is a valid line
+ *   intersection and shows up as a huge RMS: the forward model's atan(R / W) folds it back, and this function does not
+ *   guess the camera's sign convention.
+ *   xyz [3 n_tie] (TIE order): the solution; for FEW and WEAK the point's current xhat value.  quality [4 n_tie]: rays
+ *   used, lambda_min / lambda_max, RMS px linear, RMS px final (FEW: 0 0 0; WEAK: the ratio, 0 0).  status [n_tie].
+ *   *n_not_ok: this rank's points with a status other than OK.  Any output pointer may be NULL.  With world > 1 (the
+ *   subtree split included) a rank fills the tie points it owns -- all of a point's rays live on its owner -- and
+ *   writes 0 elsewhere.
+ *   write_xhat != 0: the OK and REFINE points replace their tie entries of the device xhat (FEW and WEAK keep theirs
+ *   bit for bit), which invalidates the last linearisation and the factor as fba_set_xhat does: fba_residuals and the
+ *   post-fit functions return FBA_ERR_ARG until the next iteration.  Without it the context is untouched: a following
+ *   fba_step gives bitwise the xhat it gives without the call.  Plain launches on the context's stream, fixed-order
+ *   sums (two calls are bitwise equal).  Not between fba_solve_update_async and fba_solve_finish (FBA_ERR_ARG).  With
+ *   fba_set_timing on, fba_last_timings' [7] afterwards holds the device time of this call's kernels, [0..6] 0. */
+enum { FBA_RAY_OK = 0, FBA_RAY_DOMAIN = 1 };
+enum { FBA_ISECT_OK = 0, FBA_ISECT_FEW = 1, FBA_ISECT_WEAK = 2, FBA_ISECT_REFINE = 3 };
+typedef struct fba_intersect_options {
+    int32_t refine_iters;  /* 0: linear only; default (NULL options) 10 */
+    int32_t write_xhat;    /* != 0: OK / REFINE points replace the tie entries of the device xhat */
+    double  min_ratio;     /* default (1 - cos 1deg) / 2 = 7.6e-5: two rays meeting at 1 degree */
+    double  refine_tol;    /* default 1e-10 */
+} fba_intersect_options;
+int fba_unproject_host(int32_t type, int32_t nk, int64_t n, const double* xy /*[2n]*/,
+                       const double* camtab /*[6+nk]: xp yp c ydir P1 P2 K1..Knk*/, double* out /*[5n]: xu yu d*/,
+                       int32_t* status /*[n]*/);
+int fba_image_rays(fba_ctx* ctx, double* ray /*[6 n_pts] C, d; PHO order*/, int32_t* status /*[n_pts]*/);
+int fba_intersect(fba_ctx* ctx, const fba_intersect_options* o, double* xyz /*[3 n_tie]*/,
+                  double* quality /*[4 n_tie]: rays used, lambda_min/lambda_max, rms px linear, rms px final*/,
+                  int32_t* status /*[n_tie]*/, int64_t* n_not_ok);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
