@@ -133,8 +133,8 @@ struct Sched {
     int n_top_blocks = 0;            // (lower blocks (a, b) with a, b top, the RHS block row's included)
 };
 
-// Accumulation plan (fba_capi.cpp create, run by k_lin_reduce and the k_red_* kernels): offsets
-// into the int32 device buffer Ctx::d_acc.
+// Accumulation plan (fba_plan.cpp build_plan, run by k_lin_reduce and the k_red_* kernels): offsets
+// into the int32 device buffer Ctx::d_acc (host image: HostPlan::acc).
 struct AccPlan {
     int64_t ck_cam = 0;    // [n_chunks] camera of each chunk
     int64_t ck_pk = 0;     // [n_chunks+1] pair-key range of each chunk
@@ -411,9 +411,37 @@ inline int ws_get(Ctx& c, int slot, size_t bytes, void** p) {
     return FBA_OK;
 }
 
-// kernel launchers (fba_kernels.hip / fba_chol.hip)
+// host planning (fba_order.cpp, fba_plan.cpp: no HIP call, they link without the HIP runtime)
 std::vector<int32_t> camera_order(const fba_problem* p);  // internal image slot -> EXT row or -1 (fba_order.cpp)
 void build_schedule(Ctx& c, const std::vector<std::pair<int32_t, int32_t>>& pairs);  // pairs: (e1, e2) slots, e1 > e2
+// The host images of the device arrays that build_plan decides and fba_create uploads as they are (the
+// comments of Ctx's d_<name> describe each); the plan's counts, offsets and host-side maps go to Ctx itself
+struct HostPlan {
+    std::vector<double> xy, ctl, caminfo;
+    std::vector<int32_t> img, cam, pt, lp_tie, xoff, lp_start, lp_cam, chunk_obs, chunk_pt;
+    std::vector<int32_t> acc;                 // every list of Ctx::acc and Ctx::gen
+    std::vector<int32_t> gpairs, topdiag;     // multi-rank: replicated solve / subtree split
+    std::vector<int8_t> bown, rown;
+    std::vector<uint8_t> active, counted;
+    std::vector<int32_t> pc_idx;              // priors (empty without)
+    std::vector<int64_t> pr_idx;
+    std::vector<double> pc_val, pr_val, gprior;
+};
+// what the planner would otherwise read from the environment: the caller reads it once
+struct PlanKnobs {
+    double pair_terms = 2.0;  // FBA_PAIR_TERMS: a chunk whose pair keys average <= this many terms takes the U-row path
+};
+// validation of fba_create's arguments: opt = *o or the defaults; *pr becomes nullptr for an empty list
+int check_inputs(const fba_problem* p, const fba_settings* s, const fba_options* o, const fba_priors** pr, fba_options& opt);
+// the whole host plan of one rank, from checked arguments: fills hp and the host fields of c (prob, set, opt, L,
+// img_ord, img_new, full_to_ref, xfull0, tie_owner, full_owned, obs_pho, acc, gen, sched, the n_* counts, ...)
+int build_plan(const fba_problem* p, const fba_settings* s, const fba_options& opt, const fba_priors* pr,
+               const PlanKnobs& knobs, Ctx& c, HostPlan& hp);
+int64_t count_unknowns(const fba_problem* p, const fba_settings* s);  // the reference's u
+void partition(const fba_problem* p, int world, std::vector<int32_t>& tie_owner, std::vector<int32_t>& ctl_owner);
+int image_order(const fba_problem* p, std::vector<int32_t>& order);   // checked camera_order
+
+// kernel launchers (fba_kernels.hip / fba_chol.hip)
 int launch_params(Ctx& c, const double* x = nullptr, double* copy_to = nullptr);  // x: parameters (default d_xfull),
                                                                                    // also copied to copy_to
 // raw: no whitening (fba_build_awg's A, w)
