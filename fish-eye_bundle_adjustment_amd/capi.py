@@ -30,7 +30,7 @@ EXPORTS = (
     "fba_deltasum_device", "fba_solve_finish", "fba_step", "fba_adjust",
     "fba_residuals", "fba_build_rsd", "fba_finish_stats", "fba_covariance", "fba_reliability",
     "fba_set_weights", "fba_set_loss", "fba_get_weights", "fba_last_timings", "fba_set_timing", "fba_set_probe",
-    "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve",
+    "fba_probe_stats", "fba_set_spin_bound", "fba_test_border_solve", "fba_test_live_allocations",
     "fba_set_damping", "fba_cost", "fba_adjust_lm",
     "fba_postfit_outputs",
     "fba_unproject_host", "fba_image_rays", "fba_intersect",
@@ -152,6 +152,7 @@ def _load():
         "fba_probe_stats": ([P, P], C.c_int),
         "fba_set_spin_bound": ([P, C.c_int64], C.c_int),
         "fba_test_border_solve": ([I, P, P], C.c_int),
+        "fba_test_live_allocations": ([P], C.c_int),
         "fba_set_damping": ([P, D], C.c_int),
         "fba_cost": ([P, P], C.c_int),
         "fba_adjust_lm": ([P, P, P, P, P], C.c_int),
@@ -502,6 +503,13 @@ class Context:
         ms = np.zeros(8)
         check(lib.fba_last_timings(self.h, ptr(ms)))
         return ms
+
+
+def live_allocations() -> int:
+    """(tests) fba_test_live_allocations: device and pinned allocations libfba holds in this process now"""
+    n = C.c_int64()
+    check(lib.fba_test_live_allocations(C.byref(n)))
+    return n.value
 
 
 def eig3_host(blocks):

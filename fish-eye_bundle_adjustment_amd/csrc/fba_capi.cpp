@@ -29,33 +29,10 @@ namespace fba {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-template <typename T>
-static int dalloc(T** p, size_t n) {
-    if (n == 0) n = 1;
-    FBA_HIP(hipMalloc((void**)p, n * sizeof(T)));
-    return FBA_OK;
-}
-template <typename T>
-static int upload(T** p, const std::vector<T>& v) {
-    int rc = dalloc(p, v.size());
-    if (rc) return rc;
-    if (!v.empty()) FBA_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FBA_OK;
-}
-
 static void destroy(Ctx* c) {
     if (!c) return;
-    void* ptrs[] = {c->d_chunk_obs, c->d_chunk_pt, c->d_xy, c->d_img, c->d_cam, c->d_pt, c->d_ctl, c->d_lp_tie, c->d_xoff, c->d_lrt, c->d_lp_start, c->d_lp_cam,
-                    c->d_acc, c->d_ppart, c->d_U, c->d_ipart, c->d_cpart, c->d_cseg, c->d_bscr, c->d_gblk, c->d_lrprof, c->d_ptrace, c->d_gpairs, c->d_red, c->d_xfull, c->d_xlin, c->d_delta, c->d_img_tab, c->d_cam_tab, c->d_G, c->d_J, c->d_WT,
-                    c->d_pt_tab, c->d_P, c->d_flags, c->d_S, c->d_X, c->d_dinv, c->d_linv, c->d_scal, c->d_part, c->d_res, c->d_caminfo,
-                    c->d_active, c->d_counted, c->d_obs_pho, c->d_sched, c->d_gpt, c->d_gcu, c->d_gug, c->d_xpart,
-                    c->d_kpart, c->d_bown, c->d_rown, c->d_topdiag, c->d_sw, c->d_seff, c->d_weff,
-                    c->d_pc_idx, c->d_pc_val, c->d_gprior, c->d_pr_idx, c->d_pr_val, c->d_pr_out, c->d_pr_part};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    for (auto& w : c->ws)
-        if (w.first) (void)hipFree(w.first);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
+    for (auto& q : c->owned) mem_free(q.first, q.second);
+    for (auto& w : c->ws) mem_free(w.first);
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto e : c->probe_ev)
@@ -76,20 +53,20 @@ static int upload_plan(Ctx& c, const HostPlan& hp) {
     const bool split = c.sched.split;
     int rc = FBA_OK;
     if (c.n_prior > 0 &&
-        ((c.n_pcam > 0 && ((rc = upload(&c.d_pc_idx, hp.pc_idx)) || (rc = upload(&c.d_pc_val, hp.pc_val)))) ||
-         (!hp.gprior.empty() && (rc = upload(&c.d_gprior, hp.gprior))) ||
-         (c.n_pres > 0 && ((rc = upload(&c.d_pr_idx, hp.pr_idx)) || (rc = upload(&c.d_pr_val, hp.pr_val))))))
+        ((c.n_pcam > 0 && ((rc = upload(c, &c.d_pc_idx, hp.pc_idx)) || (rc = upload(c, &c.d_pc_val, hp.pc_val)))) ||
+         (!hp.gprior.empty() && (rc = upload(c, &c.d_gprior, hp.gprior))) ||
+         (c.n_pres > 0 && ((rc = upload(c, &c.d_pr_idx, hp.pr_idx)) || (rc = upload(c, &c.d_pr_val, hp.pr_val))))))
         return rc;
-    if ((rc = upload(&c.d_xoff, hp.xoff)) || (rc = upload(&c.d_xy, hp.xy)) || (rc = upload(&c.d_img, hp.img)) ||
-        (rc = upload(&c.d_cam, hp.cam)) || (rc = upload(&c.d_pt, hp.pt)) || (rc = upload(&c.d_ctl, hp.ctl)) ||
-        (rc = upload(&c.d_lp_tie, hp.lp_tie)) || (rc = upload(&c.d_lp_start, hp.lp_start)) ||
-        (rc = upload(&c.d_lp_cam, hp.lp_cam)) || (rc = upload(&c.d_acc, hp.acc)) || (rc = upload(&c.d_xfull, c.xfull0)) ||
-        (rc = upload(&c.d_caminfo, hp.caminfo)) || (rc = upload(&c.d_active, hp.active)) ||
-        (rc = upload(&c.d_counted, hp.counted)) || (rc = upload(&c.d_obs_pho, c.obs_pho)) ||
-        (rc = upload(&c.d_chunk_obs, hp.chunk_obs)) || (rc = upload(&c.d_chunk_pt, hp.chunk_pt)) ||
-        (rc = upload(&c.d_sched, c.sched.buf)) ||
-        (c.opt.world > 1 && !split && (rc = upload(&c.d_gpairs, hp.gpairs))) ||
-        (split && ((rc = upload(&c.d_bown, hp.bown)) || (rc = upload(&c.d_rown, hp.rown)) || (rc = upload(&c.d_topdiag, hp.topdiag)))))
+    if ((rc = upload(c, &c.d_xoff, hp.xoff)) || (rc = upload(c, &c.d_xy, hp.xy)) || (rc = upload(c, &c.d_img, hp.img)) ||
+        (rc = upload(c, &c.d_cam, hp.cam)) || (rc = upload(c, &c.d_pt, hp.pt)) || (rc = upload(c, &c.d_ctl, hp.ctl)) ||
+        (rc = upload(c, &c.d_lp_tie, hp.lp_tie)) || (rc = upload(c, &c.d_lp_start, hp.lp_start)) ||
+        (rc = upload(c, &c.d_lp_cam, hp.lp_cam)) || (rc = upload(c, &c.d_acc, hp.acc)) || (rc = upload(c, &c.d_xfull, c.xfull0)) ||
+        (rc = upload(c, &c.d_caminfo, hp.caminfo)) || (rc = upload(c, &c.d_active, hp.active)) ||
+        (rc = upload(c, &c.d_counted, hp.counted)) || (rc = upload(c, &c.d_obs_pho, c.obs_pho)) ||
+        (rc = upload(c, &c.d_chunk_obs, hp.chunk_obs)) || (rc = upload(c, &c.d_chunk_pt, hp.chunk_pt)) ||
+        (rc = upload(c, &c.d_sched, c.sched.buf)) ||
+        (c.opt.world > 1 && !split && (rc = upload(c, &c.d_gpairs, hp.gpairs))) ||
+        (split && ((rc = upload(c, &c.d_bown, hp.bown)) || (rc = upload(c, &c.d_rown, hp.rown)) || (rc = upload(c, &c.d_topdiag, hp.topdiag)))))
         return rc;
     return FBA_OK;
 }
@@ -99,52 +76,51 @@ static int alloc_work(Ctx& c) {
     const Layout& L = c.L;
     const AccPlan& A = c.acc;
     const GenPlan& G = c.gen;
-    const int nj = 9 + L.cw;
-    c.ncomp = 2 * nj + 2;
-    c.pt_comp = 12 + 6 * L.cw;
-    const int npk = L.cw * (L.cw + 1) / 2 + L.cw;
+    c.ncomp = jac_stride(L.cw);
+    c.pt_comp = pt_stride(L.cw);
+    const int npk = cam_part(L.cw);
     c.n_part = (int)std::max<int64_t>((L.u_full + 255) / 256, (c.n_obs + 255) / 256 * 3) + 8;
     int rc;
-    if ((c.n_prior > 0 && ((rc = dalloc(&c.d_pr_out, (size_t)c.n_prior + 1)) || (rc = dalloc(&c.d_pr_part, (size_t)(c.n_pres + 255) / 256)))) ||
-        (rc = dalloc(&c.d_lrt, 2)) || ((c.opt.world > 1 || c.sched.split) && (rc = dalloc(&c.d_red, (size_t)c.n_red))) ||
-        (rc = dalloc(&c.d_delta, L.u_full)) || (rc = dalloc(&c.d_xlin, L.u_full)) || (rc = dalloc(&c.d_img_tab, (size_t)L.n_img * IMG_TAB)) ||
-        (rc = dalloc(&c.d_cam_tab, (size_t)L.n_cam * c.cam_tab_stride)) ||
-        (rc = dalloc(&c.d_G, (size_t)std::max(L.n_img, 1) * 42)) ||
-        (rc = dalloc(&c.d_J, (size_t)c.ncomp * c.n_obs_pad)) || (rc = dalloc(&c.d_WT, (size_t)12 * c.n_obs_pad)) ||
-        (rc = dalloc(&c.d_pt_tab, (size_t)c.pt_comp * c.n_lp_pad)) ||
-        (rc = dalloc(&c.d_ppart, (size_t)A.n_pk * 36)) ||
-        (rc = dalloc(&c.d_U, A.n_tt > 0 ? (size_t)18 * c.n_obs_pad : 1)) ||
-        (rc = dalloc(&c.d_ipart, (size_t)A.n_ik * (27 + 6 * L.cw))) ||
-        (rc = dalloc(&c.d_cpart, (size_t)(c.n_chunks_lr + G.n_gc) * npk)) ||
-        (rc = dalloc(&c.d_gpt, (size_t)G.n_gp * 18)) || (rc = dalloc(&c.d_gcu, (size_t)G.n_gc * 6 * L.cw)) ||
-        (rc = dalloc(&c.d_gug, (size_t)G.n_gi * 36)) || (rc = dalloc(&c.d_xpart, (size_t)G.n_gx * 6 * L.cw)) ||
-        (rc = dalloc(&c.d_kpart, (size_t)G.n_gkk * L.cw * L.cw)) ||
-        (rc = dalloc(&c.d_cseg, (size_t)std::max(L.n_cam, 1) * 64 * npk)) ||
-        (rc = dalloc(&c.d_bscr, (size_t)(BSC_OFF + 16))) ||  // k_border_weights / k_border_gram segments, combine coefficients, split scales
-        (rc = dalloc(&c.d_gblk, (size_t)(L.n_pad / NB) * 256)) ||
-        (rc = dalloc(&c.d_S, (size_t)(L.n_pad + NB) * L.ld)) ||
-        (rc = dalloc(&c.d_P, (size_t)std::max(c.sched.n_scratch, 1) * 4096)) || (rc = dalloc(&c.d_X, (size_t)L.n_pad)) ||
-        (rc = dalloc(&c.d_dinv, (size_t)(L.n_pad / NB) * 8 * 256)) ||
-        (rc = dalloc(&c.d_linv, (size_t)(L.n_pad / NB) * NB * NB)) ||
-        (rc = dalloc(&c.d_scal, 32 + 256)) || (rc = dalloc(&c.d_part, (size_t)c.n_part)) ||
-        (rc = dalloc(&c.d_res, (size_t)7 * std::max<int64_t>(c.n_obs, 1))))
+    if ((c.n_prior > 0 && ((rc = dalloc(c, &c.d_pr_out, (size_t)c.n_prior + 1)) || (rc = dalloc(c, &c.d_pr_part, (size_t)(c.n_pres + 255) / 256)))) ||
+        (rc = dalloc(c, &c.d_lrt, 2)) || ((c.opt.world > 1 || c.sched.split) && (rc = dalloc(c, &c.d_red, (size_t)c.n_red))) ||
+        (rc = dalloc(c, &c.d_delta, L.u_full)) || (rc = dalloc(c, &c.d_xlin, L.u_full)) || (rc = dalloc(c, &c.d_img_tab, (size_t)L.n_img * IMG_TAB)) ||
+        (rc = dalloc(c, &c.d_cam_tab, (size_t)L.n_cam * c.cam_tab_stride)) ||
+        (rc = dalloc(c, &c.d_G, (size_t)std::max(L.n_img, 1) * G_BLK)) ||
+        (rc = dalloc(c, &c.d_J, (size_t)c.ncomp * c.n_obs_pad)) || (rc = dalloc(c, &c.d_WT, (size_t)OBS_REC * c.n_obs_pad)) ||
+        (rc = dalloc(c, &c.d_pt_tab, (size_t)c.pt_comp * c.n_lp_pad)) ||
+        (rc = dalloc(c, &c.d_ppart, (size_t)A.n_pk * PAIR_BLK)) ||
+        (rc = dalloc(c, &c.d_U, A.n_tt > 0 ? (size_t)T_ROW * c.n_obs_pad : 1)) ||
+        (rc = dalloc(c, &c.d_ipart, (size_t)A.n_ik * img_part(L.cw))) ||
+        (rc = dalloc(c, &c.d_cpart, (size_t)(c.n_chunks_lr + G.n_gc) * npk)) ||
+        (rc = dalloc(c, &c.d_gpt, (size_t)G.n_gp * GPT)) || (rc = dalloc(c, &c.d_gcu, (size_t)G.n_gc * gpc_tab(L.cw))) ||
+        (rc = dalloc(c, &c.d_gug, (size_t)G.n_gi * GUG)) || (rc = dalloc(c, &c.d_xpart, (size_t)G.n_gx * xcam_part(L.cw))) ||
+        (rc = dalloc(c, &c.d_kpart, (size_t)G.n_gkk * campair_part(L.cw))) ||
+        (rc = dalloc(c, &c.d_cseg, (size_t)std::max(L.n_cam, 1) * CAM_SEG * npk)) ||
+        (rc = dalloc(c, &c.d_bscr, (size_t)BSC_TOTAL)) ||
+        (rc = dalloc(c, &c.d_gblk, (size_t)(L.n_pad / NB) * GRAM_BLK)) ||
+        (rc = dalloc(c, &c.d_S, (size_t)(L.n_pad + NB) * L.ld)) ||
+        (rc = dalloc(c, &c.d_P, (size_t)std::max(c.sched.n_scratch, 1) * 4096)) || (rc = dalloc(c, &c.d_X, (size_t)L.n_pad)) ||
+        (rc = dalloc(c, &c.d_dinv, (size_t)(L.n_pad / NB) * 8 * 256)) ||
+        (rc = dalloc(c, &c.d_linv, (size_t)(L.n_pad / NB) * NB * NB)) ||
+        (rc = dalloc(c, &c.d_scal, (size_t)SCAL_TOTAL)) || (rc = dalloc(c, &c.d_part, (size_t)c.n_part)) ||
+        (rc = dalloc(c, &c.d_res, (size_t)RES_ROW * std::max<int64_t>(c.n_obs, 1))))
         return rc;
     FBA_HIP(hipMemset(c.d_lrt, 0, 2 * sizeof(unsigned)));
-    FBA_HIP(hipMemset(c.d_scal, 0, sizeof(double) * 16));  // (chol_setup then sets scal[SCAL_SPINS])
+    FBA_HIP(hipMemset(c.d_scal, 0, sizeof(double) * SCAL_ZEROED));  // (chol_setup then sets scal[SCAL_SPINS])
     if ((rc = chol_setup(c)) || (rc = acc_setup(c))) return rc;
-    if (getenv("FBA_LR_PROFILE") && c.n_chunks_lr > 0) FBA_HIP(hipMalloc((void**)&c.d_lrprof, sizeof(uint64_t) * LR_PROF * c.n_chunks_lr));
+    if (getenv("FBA_LR_PROFILE") && c.n_chunks_lr > 0 && (rc = dalloc(c, &c.d_lrprof, (size_t)LR_PROF * c.n_chunks_lr))) return rc;
     if (getenv("FBA_PANEL_TRACE") && c.sched.n_waves > 0) {
         const size_t nt = std::max<size_t>((size_t)PTRACE_WG * c.sched.n_waves, (size_t)c.sched.flow_n * FTRACE / 8);
-        FBA_HIP(hipMalloc((void**)&c.d_ptrace, sizeof(uint64_t) * 8 * nt));
+        if ((rc = dalloc(c, &c.d_ptrace, 8 * nt))) return rc;
         FBA_HIP(hipMemset(c.d_ptrace, 0, sizeof(uint64_t) * 8 * nt));
     }
     FBA_HIP(hipMemset(c.d_delta, 0, sizeof(double) * L.u_full));
     // outside the factor's block pattern S stays zero; the pattern itself is zeroed per accumulation
     FBA_HIP(hipMemsetAsync(c.d_S, 0, sizeof(double) * (size_t)(L.n_pad + NB) * L.ld, c.stream));
     FBA_HIP(hipStreamSynchronize(c.stream));
-    FBA_HIP(hipHostMalloc((void**)&c.h_pinned, sizeof(double) * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    if ((rc = dalloc(c, &c.h_pinned, (size_t)HPIN_TOTAL, true))) return rc;
     FBA_HIP(hipHostGetDevicePointer((void**)&c.d_hpinned, c.h_pinned, 0));
-    std::fill(c.h_pinned, c.h_pinned + 64, 0.0);
+    std::fill(c.h_pinned, c.h_pinned + HPIN_TOTAL, 0.0);
     for (auto& e : c.ev) FBA_HIP(hipEventCreate(&e));
     return FBA_OK;
 }
@@ -323,7 +299,7 @@ static int solve_body(Ctx* c) {
     mark(c, 6);
     if ((rc = launch_backsub_update(*c))) return rc;
     mark(c, 7);
-    // scal[0..3] reach h_pinned from k_sum_parts itself (host-mapped stores, no copy node)
+    // the mirrored d_scal slots reach h_pinned from k_sum_parts itself (host-mapped stores, no copy node)
     return FBA_OK;
 }
 
@@ -482,7 +458,7 @@ static void print_panel_trace(Ctx* c) {
 static bool wait_solve_seq(Ctx* c) {
     if (c->force_sync || c->timing || c->d_ptrace || c->d_lrprof) return false;
     const double want = (double)c->solves_enqueued;
-    volatile const double* seq = c->h_pinned + 4;
+    volatile const double* seq = c->h_pinned + HPIN_SEQ;
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned it = 0; *seq < want; ++it) {
         if (it < 4096) continue;  // ~the first 10-20 us: spin
@@ -494,14 +470,14 @@ static bool wait_solve_seq(Ctx* c) {
 }
 
 static int solve_finish(Ctx* c, double* dsum, bool recopy) {
-    if (recopy) FBA_HIP(hipMemcpyAsync(c->h_pinned, c->d_scal, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (recopy) FBA_HIP(hipMemcpyAsync(c->h_pinned, c->d_scal, sizeof(double) * SCAL_MIRROR, hipMemcpyDeviceToHost, c->stream));
     if (recopy || !wait_solve_seq(c)) {
         FBA_HIP(hipStreamSynchronize(c->stream));
     } else {
         const hipError_t q = hipStreamQuery(c->stream);  // (hipErrorNotReady: later work queued, no error)
         if (q != hipSuccess && q != hipErrorNotReady) FBA_HIP(q);
     }
-    c->solve_seq = c->h_pinned[4];
+    c->solve_seq = c->h_pinned[HPIN_SEQ];
     if (c->d_ptrace && !c->sched.split) print_panel_trace(c);
     if (c->timing) {
         float ms;
@@ -513,8 +489,8 @@ static int solve_finish(Ctx* c, double* dsum, bool recopy) {
         c->last_ms[7] = ms;
     }
     c->iterations++;
-    const double info = c->h_pinned[1];
-    *dsum = c->h_pinned[2];
+    const double info = c->h_pinned[HPIN_FAIL];
+    *dsum = c->h_pinned[HPIN_DSUM];
     if (info < 0.0) {
         // k_update left xhat as it was (fba_chol.hip, bounded polls): the context stays usable
         set_error("device hand-off timeout in the block Cholesky / backward solve (a workgroup of k_chol_flow, "
@@ -667,29 +643,25 @@ int fba_build_awg(fba_ctx* ctx, const double* xhat, double* A, double* w, double
     if ((rc = launch_params(*c)) || (rc = launch_linearize(*c, nullptr, true))) return rc;
     const Layout& L = c->L;
     const int64_t n = 2 * c->n_pts, u = L.u_ref;
-    double *dA = nullptr, *dW = nullptr;
-    int64_t* dmap = nullptr;
-    if ((rc = dalloc(&dA, (size_t)n * u)) || (rc = dalloc(&dW, (size_t)n)) || (rc = upload(&dmap, c->full_to_ref)))
-        return rc;
-    FBA_HIP(hipMemsetAsync(dA, 0, sizeof(double) * n * u, c->stream));
-    FBA_HIP(hipMemsetAsync(dW, 0, sizeof(double) * n, c->stream));
-    if ((rc = launch_dense_awg(*c, dA, dW, dmap, n, u))) return rc;
-    if (A) FBA_HIP(hipMemcpyAsync(A, dA, sizeof(double) * n * u, hipMemcpyDeviceToHost, c->stream));
-    if (w) FBA_HIP(hipMemcpyAsync(w, dW, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    std::vector<double> g((size_t)std::max(L.n_img, 1) * 42), ct((size_t)L.n_cam * c->cam_tab_stride);
+    DevBuf<double> dA, dW;  // (freed on every return)
+    DevBuf<int64_t> dmap;
+    if ((rc = dA.alloc((size_t)n * u)) || (rc = dW.alloc((size_t)n)) || (rc = dmap.upload(c->full_to_ref))) return rc;
+    FBA_HIP(hipMemsetAsync(dA.get(), 0, sizeof(double) * n * u, c->stream));
+    FBA_HIP(hipMemsetAsync(dW.get(), 0, sizeof(double) * n, c->stream));
+    if ((rc = launch_dense_awg(*c, dA.get(), dW.get(), dmap.get(), n, u))) return rc;
+    if (A) FBA_HIP(hipMemcpyAsync(A, dA.get(), sizeof(double) * n * u, hipMemcpyDeviceToHost, c->stream));
+    if (w) FBA_HIP(hipMemcpyAsync(w, dW.get(), sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    std::vector<double> g((size_t)std::max(L.n_img, 1) * G_BLK), ct((size_t)L.n_cam * c->cam_tab_stride);
     FBA_HIP(hipMemcpyAsync(g.data(), c->d_G, sizeof(double) * g.size(), hipMemcpyDeviceToHost, c->stream));
     FBA_HIP(hipMemcpyAsync(ct.data(), c->d_cam_tab, sizeof(double) * ct.size(), hipMemcpyDeviceToHost, c->stream));
     FBA_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(dA);
-    (void)hipFree(dW);
-    (void)hipFree(dmap);
     if (G && c->set.inner_constraints) {
-        std::fill(G, G + u * 7, 0.0);
+        std::fill(G, G + u * G_ROW, 0.0);
         for (int e = 0; e < L.n_img; ++e)
             for (int a = 0; a < 6; ++a) {
                 const int64_t r = c->full_to_ref[6 * (int64_t)e + a];
                 if (r < 0) continue;  // padding slot
-                for (int m = 0; m < 7; ++m) G[r + m * u] = g[(size_t)e * 42 + a * 7 + m];
+                for (int m = 0; m < G_ROW; ++m) G[r + m * u] = g[(size_t)e * G_BLK + a * G_ROW + m];
             }
     }
     if (dist_scaling) {
@@ -754,7 +726,7 @@ int fba_solve_update_async(fba_ctx* ctx) {
 int fba_deltasum_device(fba_ctx* ctx, void** dev_ptr) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !dev_ptr) { set_error("NULL argument"); return FBA_ERR_ARG; }
-    *dev_ptr = c->d_scal + 2;
+    *dev_ptr = c->d_scal + SCAL_DSUM;
     return FBA_OK;
 }
 
@@ -809,19 +781,19 @@ int fba_residuals(fba_ctx* ctx, double* v, double* rsd, double* stats) {
         return rc;
     const int64_t n = c->n_obs;
     const int nblk = (int)((n + 255) / 256);
-    std::vector<double> res(7 * (size_t)n), part(3 * (size_t)nblk);
+    std::vector<double> res(RES_ROW * (size_t)n), part(3 * (size_t)nblk);
     if (n > 0) {
         FBA_HIP(hipMemcpyAsync(res.data(), c->d_res, sizeof(double) * res.size(), hipMemcpyDeviceToHost, c->stream));
         FBA_HIP(hipMemcpyAsync(part.data(), c->d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c->stream));
     }
     FBA_HIP(hipStreamSynchronize(c->stream));
     if (v) std::fill(v, v + 2 * c->n_pts, 0.0);
-    if (rsd) std::fill(rsd, rsd + 5 * c->n_pts, 0.0);
+    if (rsd) std::fill(rsd, rsd + RSD_ROW * c->n_pts, 0.0);
     for (int64_t o = 0; o < n; ++o) {
         const int64_t i = c->obs_pho[o];
         if (v) { v[2 * i] = res[2 * o]; v[2 * i + 1] = res[2 * o + 1]; }
         if (rsd)
-            for (int m = 0; m < 5; ++m) rsd[5 * i + m] = res[2 * n + 5 * o + m];
+            for (int m = 0; m < RSD_ROW; ++m) rsd[RSD_ROW * i + m] = res[2 * n + RSD_ROW * o + m];
     }
     double sx = 0, sy = 0, sp = 0;
     for (int b = 0; b < nblk; ++b) { sx += part[3 * b]; sy += part[3 * b + 1]; sp += part[3 * b + 2]; }
@@ -852,7 +824,7 @@ static int weight_buffers(Ctx* c) {
     if (c->d_sw) return FBA_OK;
     const size_t n = 2 * (size_t)std::max<int64_t>(c->n_obs, 1);
     int rc;
-    if ((rc = dalloc(&c->d_sw, n)) || (rc = dalloc(&c->d_seff, n)) || (rc = dalloc(&c->d_weff, n))) return rc;
+    if ((rc = dalloc(*c, &c->d_sw, n)) || (rc = dalloc(*c, &c->d_seff, n)) || (rc = dalloc(*c, &c->d_weff, n))) return rc;
     return FBA_OK;
 }
 // a change of the weighting: the captured accumulation holds the old kernel arguments, and neither the
@@ -895,7 +867,7 @@ int fba_set_weights(fba_ctx* ctx, const double* weight) {
     }
     if ((rc = weight_buffers(c))) return rc;
     double* d_w = nullptr;
-    if ((rc = ws_get(*c, 72, sizeof(double) * (size_t)std::max<int64_t>(n, 1), (void**)&d_w))) return rc;
+    if ((rc = ws_get(*c, WS_WEIGHTS, (size_t)n, &d_w))) return rc;
     if (n > 0) FBA_HIP(hipMemcpyAsync(d_w, weight, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_set_weights(*c, d_w))) return rc;
     FBA_HIP(hipStreamSynchronize(c->stream));
@@ -937,7 +909,7 @@ int fba_get_weights(fba_ctx* ctx, double* weight) {
     if ((rc = launch_params(*c, c->d_xlin)) || (rc = launch_linearize(*c, c->d_xlin)) || (rc = launch_residuals(*c)))
         return rc;
     double* d_w = nullptr;
-    if ((rc = ws_get(*c, 72, sizeof(double) * (size_t)std::max<int64_t>(n, 1), (void**)&d_w))) return rc;
+    if ((rc = ws_get(*c, WS_WEIGHTS, (size_t)n, &d_w))) return rc;
     if (n > 0) FBA_HIP(hipMemsetAsync(d_w, 0, sizeof(double) * n, c->stream));
     if ((rc = launch_get_weights(*c, d_w))) return rc;
     if (n > 0) FBA_HIP(hipMemcpyAsync(weight, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
@@ -985,7 +957,7 @@ int fba_cost(fba_ctx* ctx, double* cost) {
     const size_t nblk = (size_t)((c->n_obs + 255) / 256);
     double* d_w = nullptr;
     int rc;
-    if ((rc = ws_get(*c, 73, sizeof(double) * (nblk + 4), (void**)&d_w)) || (rc = launch_cost(*c, d_w + 4, d_w))) return rc;
+    if ((rc = ws_get(*c, WS_COST, nblk + 4, &d_w)) || (rc = launch_cost(*c, d_w + 4, d_w))) return rc;
     FBA_HIP(hipMemcpyAsync(cost, d_w, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
     FBA_HIP(hipStreamSynchronize(c->stream));
     return FBA_OK;
@@ -1008,7 +980,7 @@ int fba_adjust_lm(fba_ctx* ctx, const fba_lm_options* o, int32_t* trials, int32_
     const size_t xbytes = sizeof(double) * (size_t)c->L.u_full;
     double* d_save = nullptr;
     int rc, n = 0, nt = 0;
-    if ((rc = ws_get(*c, 74, std::max<size_t>(xbytes, 8), (void**)&d_save))) return rc;
+    if ((rc = ws_get(*c, WS_LM_SAVE, (size_t)c->L.u_full, &d_save))) return rc;
     auto record = [&](double lambda, double cost, double dsum, int acc) {
         if (hist) { hist[4 * n] = lambda; hist[4 * n + 1] = cost; hist[4 * n + 2] = dsum; hist[4 * n + 3] = acc; }
         ++n;
@@ -1089,28 +1061,23 @@ int fba_build_rsd(fba_ctx* ctx, const double* v, const double* xhat, double* rsd
             xpyp[2 * k + a] = c->full_to_ref[f] >= 0 ? xhat[c->full_to_ref[f]] : c->xfull0[f];
         }
     const int64_t n = c->n_pts;
-    double *dv = nullptr, *dx = nullptr, *dr = nullptr;
+    DevBuf<double> dv, dx, dr;  // (freed on every return)
     int rc;
-    auto release = [&]() { for (void* q : {(void*)dv, (void*)dx, (void*)dr}) if (q) (void)hipFree(q); };
-    if ((rc = dalloc(&dv, 2 * (size_t)n)) || (rc = upload(&dx, xpyp)) || (rc = dalloc(&dr, 5 * (size_t)n))) { release(); return rc; }
-    hipError_t e = hipMemcpyAsync(dv, v, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dr, 0, sizeof(double) * 5 * n, c->stream);
-    if (e == hipSuccess && (rc = launch_build_rsd(*c, dv, dx, dr))) { release(); return rc; }
-    if (e == hipSuccess) e = hipMemcpyAsync(rsd, dr, sizeof(double) * 5 * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release();
-    if (e != hipSuccess) { set_error(std::string("HIP error in fba_build_rsd: ") + hipGetErrorString(e)); return FBA_ERR_HIP; }
+    if ((rc = dv.alloc(2 * (size_t)n)) || (rc = dx.upload(xpyp)) || (rc = dr.alloc(RSD_ROW * (size_t)n))) return rc;
+    FBA_HIP(hipMemcpyAsync(dv.get(), v, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    FBA_HIP(hipMemsetAsync(dr.get(), 0, sizeof(double) * RSD_ROW * n, c->stream));
+    if ((rc = launch_build_rsd(*c, dv.get(), dx.get(), dr.get()))) return rc;
+    FBA_HIP(hipMemcpyAsync(rsd, dr.get(), sizeof(double) * RSD_ROW * n, hipMemcpyDeviceToHost, c->stream));
+    FBA_HIP(hipStreamSynchronize(c->stream));
     return FBA_OK;
 }
 
 // fba_covariance, and with rel fba_reliability: the same launches and host code for cx_diag / corr, then the
 // reliability kernels on the same selected inverse (redundancy / wstat [2 n_pts], either may be NULL)
-// postfit (fba_postfit_outputs): launch_postfit instead of the two older drivers -- the same launches for the four
-// outputs above, then the tie points' full blocks (cx_tie [6 n_tie], TIE order) and their ellipsoids (ellipsoid
-// [12 n_tie]); either may be NULL, the ellipsoids alone keep the blocks in workspace
+// fba_postfit_outputs: besides those four, the tie points' full blocks (cx_tie [TIE_BLK n_tie], TIE order) and their
+// ellipsoids (ellipsoid [ELL_OUT n_tie]); either may be NULL, the ellipsoids alone keep the blocks in workspace
 static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_diag, double* corr, bool rel,
-                           double* redundancy, double* wstat, bool postfit = false, double* cx_tie = nullptr,
-                           double* ellipsoid = nullptr) {
+                           double* redundancy, double* wstat, double* cx_tie = nullptr, double* ellipsoid = nullptr) {
     if (!c) { set_error("NULL context"); return FBA_ERR_ARG; }
     if (rel && c->sched.split) {
         set_error(std::string(who) + ": redundancy / wstat are not implemented for the subtree split (fba_solve_mode 1); "
@@ -1131,52 +1098,44 @@ static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_d
         islot[e] = c->img_new[e];
         icam[e] = std::max(c->ref_img_cam[e], 0);
     }
-    auto release = [&]() {};  // (the context's workspace slots 64..68, kept for the next call)
-    int rc;
-    if ((rc = ws_get(*c, 64, sizeof(double) * std::max<int64_t>(L.u_c, 1), (void**)&d_cdiag)) ||
-        (rc = ws_get(*c, 65, sizeof(double) * 3 * (size_t)std::max(L.n_tie, 1), (void**)&d_pdiag)) ||
-        (corr && (rc = ws_get(*c, 66, sizeof(double) * (size_t)std::max(L.n_img_ref, 1) * m * m, (void**)&d_iblk))) ||
-        (rc = ws_get(*c, 67, sizeof(int32_t) * islot.size(), (void**)&d_islot)) ||
-        (rc = ws_get(*c, 68, sizeof(int32_t) * icam.size(), (void**)&d_icam))) {
+    int rc;  // (all device scratch is the context's workspace, kept for the next call)
+    if ((rc = ws_get(*c, WS_CDIAG, (size_t)L.u_c, &d_cdiag)) ||
+        (rc = ws_get(*c, WS_PDIAG, 3 * (size_t)std::max(L.n_tie, 1), &d_pdiag)) ||
+        (corr && (rc = ws_get(*c, WS_IBLK, (size_t)std::max(L.n_img_ref, 1) * m * m, &d_iblk))) ||
+        (rc = ws_get(*c, WS_ISLOT, islot.size(), &d_islot)) || (rc = ws_get(*c, WS_ICAM, icam.size(), &d_icam)))
         return rc;
-    }
     if (hipMemcpyAsync(d_islot, islot.data(), sizeof(int32_t) * islot.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(d_icam, icam.data(), sizeof(int32_t) * icam.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
         set_error("hipMemcpyAsync failed");
         return FBA_ERR_HIP;
     }
     if (hipMemsetAsync(d_pdiag, 0, sizeof(double) * 3 * std::max(L.n_tie, 1), c->stream) != hipSuccess) {
-        release();
         set_error("hipMemsetAsync failed");
         return FBA_ERR_HIP;
     }
     double *d_q = nullptr, *d_red = nullptr, *d_wst = nullptr;
-    if (rel && ((rc = ws_get(*c, 69, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_obs, 1), (void**)&d_q)) ||
-                (rc = ws_get(*c, 70, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_red)) ||
-                (rc = ws_get(*c, 71, sizeof(double) * 2 * (size_t)std::max<int64_t>(c->n_pts, 1), (void**)&d_wst))))
+    if (rel && ((rc = ws_get(*c, WS_REL_Q, 2 * (size_t)std::max<int64_t>(c->n_obs, 1), &d_q)) ||
+                (rc = ws_get(*c, WS_REL_RED, 2 * (size_t)std::max<int64_t>(c->n_pts, 1), &d_red)) ||
+                (rc = ws_get(*c, WS_REL_WST, 2 * (size_t)std::max<int64_t>(c->n_pts, 1), &d_wst))))
         return rc;
     double *d_blk = nullptr, *d_ell = nullptr;
     const size_t nt = (size_t)std::max(L.n_tie, 1);
-    if (((cx_tie || ellipsoid) && (rc = ws_get(*c, 72, sizeof(double) * 6 * nt, (void**)&d_blk))) ||
-        (ellipsoid && (rc = ws_get(*c, 73, sizeof(double) * 12 * nt, (void**)&d_ell))))
+    if (((cx_tie || ellipsoid) && (rc = ws_get(*c, WS_TIE_BLK, TIE_BLK * nt, &d_blk))) ||
+        (ellipsoid && (rc = ws_get(*c, WS_ELLIPSOID, ELL_OUT * nt, &d_ell))))
         return rc;
-    if ((rc = postfit ? launch_postfit(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst,
-                                       sigma02, d_blk, d_ell)
-              : rel   ? launch_reliability(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst)
-                      : launch_covariance(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0))) {
-        release();
+    if ((rc = launch_postfit(*c, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, corr ? L.n_img_ref : 0, d_q, d_red, d_wst, sigma02,
+                             d_blk, d_ell)))
         return rc;
-    }
     if (L.n_tie > 0 && (cx_tie || ellipsoid)) {
-        if ((cx_tie && hipMemcpy(cx_tie, d_blk, sizeof(double) * 6 * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess) ||
-            (ellipsoid && hipMemcpy(ellipsoid, d_ell, sizeof(double) * 12 * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess)) {
+        if ((cx_tie && hipMemcpy(cx_tie, d_blk, sizeof(double) * TIE_BLK * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (ellipsoid && hipMemcpy(ellipsoid, d_ell, sizeof(double) * ELL_OUT * (size_t)L.n_tie, hipMemcpyDeviceToHost) != hipSuccess)) {
             set_error("HIP error copying the tie points' blocks back");
             return FBA_ERR_HIP;
         }
         // (another rank's points: zeros, so that the ranks' outputs sum; their blocks are zero already)
         if (ellipsoid)
             for (int t = 0; t < L.n_tie; ++t)
-                if (!c->full_owned[L.u_c + 3 * (int64_t)t]) std::fill(ellipsoid + 12 * (size_t)t, ellipsoid + 12 * (size_t)t + 12, 0.0);
+                if (!c->full_owned[L.u_c + 3 * (int64_t)t]) std::fill(ellipsoid + ELL_OUT * (size_t)t, ellipsoid + ELL_OUT * (size_t)t + ELL_OUT, 0.0);
     }
     if (rel && c->n_pts > 0) {
         const size_t nb = sizeof(double) * 2 * (size_t)c->n_pts;
@@ -1190,7 +1149,6 @@ static int covariance_impl(Ctx* c, const char* who, double sigma02, double* cx_d
     const hipError_t e1 = hipMemcpy(cd.data(), d_cdiag, sizeof(double) * cd.size(), hipMemcpyDeviceToHost);
     const hipError_t e2 = pd.empty() ? hipSuccess : hipMemcpy(pd.data(), d_pdiag, sizeof(double) * pd.size(), hipMemcpyDeviceToHost);
     const hipError_t e3 = ib.empty() ? hipSuccess : hipMemcpy(ib.data(), d_iblk, sizeof(double) * ib.size(), hipMemcpyDeviceToHost);
-    release();
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
         set_error("HIP error copying the covariance back");
         return FBA_ERR_HIP;
@@ -1248,12 +1206,12 @@ int fba_reliability(fba_ctx* ctx, double sigma02, double* cx_diag, double* corr,
 int fba_postfit_outputs(fba_ctx* ctx, double sigma02, const fba_postfit* out) {
     if (!out) { set_error("fba_postfit_outputs: NULL output structure"); return FBA_ERR_ARG; }
     return covariance_impl(reinterpret_cast<Ctx*>(ctx), "fba_postfit_outputs", sigma02, out->cx_diag, out->corr,
-                           out->redundancy || out->wstat, out->redundancy, out->wstat, true, out->cx_tie, out->ellipsoid);
+                           out->redundancy || out->wstat, out->redundancy, out->wstat, out->cx_tie, out->ellipsoid);
 }
 
 int fba_eig3_host(int64_t n, const double* blk, double* ell) {
     if (n < 0 || (n > 0 && (!blk || !ell))) { set_error("fba_eig3_host: NULL argument"); return FBA_ERR_ARG; }
-    for (int64_t i = 0; i < n; ++i) eig3_block(blk + 6 * i, ell + 12 * i);
+    for (int64_t i = 0; i < n; ++i) eig3_block(blk + TIE_BLK * i, ell + ELL_OUT * i);
     return FBA_OK;
 }
 
@@ -1276,12 +1234,12 @@ int fba_unproject_host(int32_t type, int32_t nk, int64_t n, const double* xy, co
 }
 
 namespace fba {
-// the rays of this rank's observations at d_xfull into workspace (local order): ray [6 n_obs], rst [n_obs], xu [2 n_obs]
+// the rays of this rank's observations at d_xfull into workspace (local order): ray [RAY_REC n_obs], rst [n_obs], xu [2 n_obs]
 static int rays_to_ws(Ctx* c, double** d_ray, int32_t** d_rst, double** d_xu) {
     const size_t n = (size_t)std::max<int64_t>(c->n_obs, 1);
     int rc;
-    if ((rc = ws_get(*c, 80, sizeof(double) * 6 * n, (void**)d_ray)) || (rc = ws_get(*c, 81, sizeof(int32_t) * n, (void**)d_rst)) ||
-        (rc = ws_get(*c, 82, sizeof(double) * 2 * n, (void**)d_xu)))
+    if ((rc = ws_get(*c, WS_RAY, RAY_REC * n, d_ray)) || (rc = ws_get(*c, WS_RAY_ST, n, d_rst)) ||
+        (rc = ws_get(*c, WS_RAY_XU, 2 * n, d_xu)))
         return rc;
     // the image / camera tables at d_xfull: functions of xhat alone, so between fba_accumulate and fba_solve_update
     // they are rewritten with the values they hold (launch_cost's argument)
@@ -1299,18 +1257,18 @@ int fba_image_rays(fba_ctx* ctx, double* ray, int32_t* status) {
     int rc;
     if ((rc = rays_to_ws(c, &d_ray, &d_rst, &d_xu))) return rc;
     const int64_t n = c->n_obs;
-    std::vector<double> hr(6 * (size_t)n);
+    std::vector<double> hr(RAY_REC * (size_t)n);
     std::vector<int32_t> hs((size_t)n);
     if (n > 0) {
         FBA_HIP(hipMemcpyAsync(hr.data(), d_ray, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, c->stream));
         FBA_HIP(hipMemcpyAsync(hs.data(), d_rst, sizeof(int32_t) * hs.size(), hipMemcpyDeviceToHost, c->stream));
     }
     FBA_HIP(hipStreamSynchronize(c->stream));
-    if (ray) std::fill(ray, ray + 6 * c->n_pts, 0.0);
+    if (ray) std::fill(ray, ray + RAY_REC * c->n_pts, 0.0);
     if (status) std::fill(status, status + c->n_pts, 0);
     for (int64_t o = 0; o < n; ++o) {  // local order -> PHO order; another rank's rows stay 0
         const int64_t i = c->obs_pho[o];
-        if (ray) std::copy(hr.begin() + 6 * o, hr.begin() + 6 * o + 6, ray + 6 * i);
+        if (ray) std::copy(hr.begin() + RAY_REC * o, hr.begin() + RAY_REC * o + RAY_REC, ray + RAY_REC * i);
         if (status) status[i] = hs[o];
     }
     return FBA_OK;
@@ -1332,7 +1290,7 @@ int fba_intersect(fba_ctx* ctx, const fba_intersect_options* o, double* xyz, dou
     double *d_ray = nullptr, *d_xu = nullptr, *d_out = nullptr;
     int32_t *d_rst = nullptr, *d_st = nullptr;
     int rc;
-    if ((rc = ws_get(*c, 83, sizeof(double) * 7 * nt, (void**)&d_out)) || (rc = ws_get(*c, 84, sizeof(int32_t) * nt, (void**)&d_st)))
+    if ((rc = ws_get(*c, WS_ISECT_OUT, 7 * nt, &d_out)) || (rc = ws_get(*c, WS_ISECT_ST, nt, &d_st)))
         return rc;
     // another rank's tie points stay 0 (the ranks' outputs sum to the whole)
     FBA_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * 7 * nt, c->stream));
@@ -1414,6 +1372,12 @@ int fba_probe_stats(fba_ctx* ctx, double* out) {
     out[1] = ms;
     out[2] = c->probe_flops;
     out[3] = 0.0;
+    return FBA_OK;
+}
+
+int fba_test_live_allocations(int64_t* n) {
+    if (!n) { set_error("NULL argument"); return FBA_ERR_ARG; }
+    *n = g_live_allocations.load(std::memory_order_relaxed);
     return FBA_OK;
 }
 

@@ -79,25 +79,25 @@ __device__ __forceinline__ double2 ld_sc1(__amdgpu_buffer_rsrc_t r, int64_t off_
 }
 // Bounded polls.  Every wait in this file gives up after scal[SCAL_SPINS] sleeps (the context's bound:
 // default 1 << 22, ~0.3 s; FBA_FLAG_SPINS at context creation lowers it, to force the path in a test) and then
-// RAISES THE ABORT: scal[1] = -1.0 (agent-scope store).  Every other poll checks the abort word every 64
+// RAISES THE ABORT: scal[SCAL_FAIL] = -1.0 (agent-scope store).  Every other poll checks the abort word every 64
 // sleeps (not on its first miss: that load would sit on every hand-off's critical path) and stops too, so
 // after one expiry the whole launch drains within about a millisecond; a k_chol_flow record that has not started yet is skipped entirely, k_bwd_flow's
 // workgroups return at once, and k_update leaves xhat untouched (fba_kernels.hip): the step fails with
 // FBA_ERR_HIP and xhat is as before it.  The sync words are zeroed again ahead of the next factorisation
 // (k_border_rhs), so a later step runs normally.
 __device__ __forceinline__ bool hand_off_aborted(const double* scal) {  // the timeout mark, sign bit of -1.0
-    return (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(scal + 1), __ATOMIC_RELAXED,
+    return (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(scal + SCAL_FAIL), __ATOMIC_RELAXED,
                                         __HIP_MEMORY_SCOPE_AGENT) < 0;
 }
 __device__ __forceinline__ void hand_off_abort(double* scal) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(scal + 1), __builtin_bit_cast(unsigned long long, -1.0),
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(scal + SCAL_FAIL), __builtin_bit_cast(unsigned long long, -1.0),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// a non-positive pivot in the block at row k0: the first one is reported (scal[1] = k0 + 1) unless a
+// a non-positive pivot in the block at row k0: the first one is reported (scal[SCAL_FAIL] = k0 + 1) unless a
 // hand-off already aborted (a compare-and-swap from 0, so it never overwrites the abort mark)
 __device__ __forceinline__ void pivot_failed(double* scal, int64_t k0) {
     unsigned long long zero = 0ull;
-    __hip_atomic_compare_exchange_strong(reinterpret_cast<unsigned long long*>(scal + 1), &zero,
+    __hip_atomic_compare_exchange_strong(reinterpret_cast<unsigned long long*>(scal + SCAL_FAIL), &zero,
                                          __builtin_bit_cast(unsigned long long, (double)(k0 + 1)), __ATOMIC_RELAXED,
                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -567,7 +567,7 @@ __device__ __forceinline__ void fset_tile(int set, int idx, int& ta, int& tb) { 
 //   wave 4      (wave 0's SIMD, mostly asleep) stores block column s and D_s once column s is solved,
 //               and with a flag publishes them
 // Every wait points to work that does not wait for the waiter, so the chain always progresses; the
-// polls are bounded (scal[1] = -1 on timeout, reported by the host).
+// polls are bounded (scal[SCAL_FAIL] = -1 on timeout, reported by the host).
 // PRE: the block's lower tiles are already in LDS (k_chol_flow's diagonal workgroup updated them there)
 // hpart (flag hflag): the split helper's partial of the tiles of tile columns >= FLOW_CSPLIT (fset 2 order,
 // 16 x 16 row-major each), added by the bulk waves at their step FLOW_CSPLIT - 2, between the trailing
@@ -1397,17 +1397,16 @@ __global__ __launch_bounds__(256) void k_syrk_multi(double* __restrict__ S, int6
 // border combine (inner constraints): RHS rows n_pad + 0 (y) and n_pad + 1..7 (Z), length n
 // ------------------------------------------------------------------------------------------------
 // k_border_gram: the Gram matrix of the 15 forward-solved RHS rows [y | A (7) | B (7)]: GRAM_SEG
-// workgroups, each a contiguous range of 128-column tiles staged through LDS, the 120 entries (a <= b)
-// of its range into gpart[seg][120]
-constexpr int GRAM_SEG = 16;
+// workgroups, each a contiguous range of 128-column tiles staged through LDS, the GRAM_N entries (a <= b)
+// of its range into gpart[seg][GRAM_N]
 
 __global__ __launch_bounds__(256) void k_border_gram(const double* __restrict__ S, int64_t ld, int64_t n_pad,
                                                      double* __restrict__ gpart) {
     __shared__ double R[15][CB + 1];
-    __shared__ double half[2][120];
+    __shared__ double half[2][GRAM_N];
     const int tid = threadIdx.x, seg = blockIdx.x;
     const int64_t nt = n_pad / CB, t0 = nt * seg / GRAM_SEG, t1 = nt * (seg + 1) / GRAM_SEG;
-    const int e = tid % 120, h = tid / 120;  // threads 0..239: entry e, half h of the 128 columns
+    const int e = tid % GRAM_N, h = tid / GRAM_N;  // threads 0..239: entry e, half h of the 128 columns
     int a = 0, rem = e;
     while (rem >= 15 - a) { rem -= 15 - a; ++a; }
     const int b = a + rem;
@@ -1431,7 +1430,7 @@ __global__ __launch_bounds__(256) void k_border_gram(const double* __restrict__ 
     }
     if (h < 2) half[h][e] = v;
     __syncthreads();
-    if (tid < 120) gpart[(int64_t)seg * 120 + tid] = half[0][tid] + half[1][tid];
+    if (tid < GRAM_N) gpart[(int64_t)seg * GRAM_N + tid] = half[0][tid] + half[1][tid];
 }
 
 // k_border_combine: every workgroup adds the Gram segments (fixed order), solves
@@ -1447,7 +1446,7 @@ __device__ __forceinline__ void border_combine_body(const double* __restrict__ g
                                                     int nblk, double (*g)[15], double* coef,
                                                     const double* __restrict__ bsc = nullptr) {
     const int tid = threadIdx.x;
-    if (tid < 120) {
+    if (tid < GRAM_N) {
         int a = 0, rem = tid;
         while (rem >= 15 - a) { rem -= 15 - a; ++a; }
         const int b = a + rem;
@@ -1456,7 +1455,7 @@ __device__ __forceinline__ void border_combine_body(const double* __restrict__ g
             for (int q = 0; q < nblk; q += 32) {  // 32 loads in flight, the same running sum
                 double x[32];
 #pragma unroll
-                for (int u = 0; u < 32; ++u) x[u] = q + u < nblk ? gblk[(int64_t)(q + u) * 256 + a * 16 + b] : 0.0;
+                for (int u = 0; u < 32; ++u) x[u] = q + u < nblk ? gblk[(int64_t)(q + u) * GRAM_BLK + a * 16 + b] : 0.0;
 #pragma unroll
                 for (int u = 0; u < 32; ++u)
                     if (q + u < nblk) v += x[u];
@@ -1464,7 +1463,7 @@ __device__ __forceinline__ void border_combine_body(const double* __restrict__ g
         } else {
             double x[GRAM_SEG];
 #pragma unroll
-            for (int q = 0; q < GRAM_SEG; ++q) x[q] = gpart[q * 120 + tid];
+            for (int q = 0; q < GRAM_SEG; ++q) x[q] = gpart[q * GRAM_N + tid];
 #pragma unroll
             for (int q = 0; q < GRAM_SEG; ++q) v += x[q];
         }
@@ -2573,7 +2572,7 @@ __device__ __forceinline__ void flow_record(int rid, double* __restrict__ S, int
         wait_list_sc1(lists + rec[3], rec[4], fl, scal);  // the final writers of the panel block's quarters
         if (tr && threadIdx.x == 0) tr[1] = wall_clock64();
         trsm_flow_body(S, ld, rec + 1, dinv, colflags + rec[1], scal, smem, tr, fl + rec[5],
-                       (gblk && rec[7] >= 0) ? gblk + (int64_t)rec[7] * 256 : nullptr);
+                       (gblk && rec[7] >= 0) ? gblk + (int64_t)rec[7] * GRAM_BLK : nullptr);
     } else if (role == 2) {
         if (rec[3] == 4) syrk_block_body(S, ld, rec, lists, P, fl, cnt, scal, smem, tr);
         else syrk_flow_body(S, ld, rec, lists, P, fl, cnt, scal, smem, tr);
@@ -2706,7 +2705,7 @@ __global__ __launch_bounds__(256) void k_bwd_wave(double* __restrict__ S, int64_
 // x_j = Linv_j' (y_j - sum), published write-through, and delta_c = -x_j stored (k_neg_copy fused).  Roles
 // come from an atomic ticket in start order and waits only point to higher blocks (earlier tickets), so
 // they end whether or not the whole grid is co-resident; polls are
-// bounded (scal[1] = -1 on timeout, reported by the host).
+// bounded (scal[SCAL_FAIL] = -1 on timeout, reported by the host).
 // With inner constraints and `combine`, one more workgroup (ticket 0) solves the border's 14x14
 // system (border_combine_body) meanwhile, publishes the coefficients write-through and raises flags[nb];
 // the block workgroups wait for it only where they form u_j (after staging and their sources).
@@ -2972,7 +2971,7 @@ int launch_cholesky(Ctx& c, int part) {
             // [panel solves][inverses of the previous level's blocks]; U = the previous level (merged)
             k_panel<<<(unsigned)(W.ncol + W.ntrsm + nprev + (U ? U->ntask : 0)), POTRF_THREADS, PANEL_LDS, c.stream>>>(
                 c.d_S, ld, c.d_sched + W.cols, W.ncol, c.d_sched + W.trsm, W.ntrsm, prev, nprev, c.d_dinv, c.d_linv,
-                c.d_scal, c.d_flags, (int)c.panel_progressive, U ? c.d_sched + U->tasks : nullptr, U ? U->ntask : 0,
+                c.d_scal, c.d_flags, /*progressive*/ 1, U ? c.d_sched + U->tasks : nullptr, U ? U->ntask : 0,
                 U ? U->ndiag : 0, U ? U->npanel : 0, U ? c.d_sched + U->src : nullptr, c.d_P,
                 U ? c.d_sched + U->comb : nullptr,
                 U ? c.d_counters + U->cbase : nullptr, c.d_tflags, c.d_sched + W.wstart, c.d_sched + W.wlist,
@@ -2991,8 +2990,7 @@ int launch_cholesky(Ctx& c, int part) {
         }
         pend = -1;
         if (W.ntask == 0) continue;
-        if (c.merge_updates) pend = w;  // into the next level's k_panel
-        else updates(w);
+        pend = w;  // into the next level's k_panel
     }
     if (pend >= 0) updates(pend);
     FBA_HIP(hipGetLastError());
@@ -3018,21 +3016,15 @@ int launch_backward_rows(Ctx& c, int row0, int nrows, double* X) {
 // placed in Gram segment 0 (the other segments zero)
 int border_solve_selftest(int device, const double* gram, double* coef) {
     FBA_HIP(hipSetDevice(device));
-    std::vector<double> gp((size_t)GRAM_SEG * 120, 0.0);
+    std::vector<double> gp((size_t)GRAM_SEG * GRAM_N, 0.0);
     for (int e = 0, a = 0; a < 15; ++a)
         for (int b = a; b < 15; ++b, ++e) gp[e] = gram[a * 15 + b];
-    double *dg = nullptr, *dc = nullptr;
-    FBA_HIP(hipMalloc((void**)&dg, gp.size() * sizeof(double)));
-    hipError_t e1 = hipMalloc((void**)&dc, 16 * sizeof(double));
-    if (e1 == hipSuccess) e1 = hipMemcpy(dg, gp.data(), gp.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e1 == hipSuccess) {
-        k_border_combine<<<1, 256>>>(nullptr, 0, 0, dg, dc);
-        e1 = hipGetLastError();
-    }
-    if (e1 == hipSuccess) e1 = hipMemcpy(coef, dc, 14 * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(dg);
-    if (dc) (void)hipFree(dc);
-    FBA_HIP(e1);
+    DevBuf<double> dg, dc;
+    int rc;
+    if ((rc = dg.upload(gp)) || (rc = dc.alloc(16))) return rc;
+    k_border_combine<<<1, 256>>>(nullptr, 0, 0, dg.get(), dc.get());
+    FBA_HIP(hipGetLastError());
+    FBA_HIP(hipMemcpy(coef, dc.get(), BORDER_COLS * sizeof(double), hipMemcpyDeviceToHost));
     return FBA_OK;
 }
 
@@ -3059,7 +3051,7 @@ int launch_backward(Ctx& c) {
     const Sched& s = c.sched;
     const int64_t nb = c.L.n_pad / CB;
     const bool flow = c.bwd_flow;  // (ticket-ordered roles: no co-residency requirement)
-    double* coef = c.d_bscr + 32 * 14 + 16 * 120;
+    double* coef = c.d_bscr + BSC_COEF;
     const bool gblk = c.chol_flow && s.flow_ok && (s.flow_n > 0 || s.split);
     // the combine inside k_bwd_flow (one more workgroup) when the Gram comes from k_chol_flow
     const int combine = (c.set.inner_constraints && flow && gblk) ? 1 : 0;
@@ -3068,20 +3060,20 @@ int launch_backward(Ctx& c) {
         // iteration graph adds cross-queue waits to every launch of the Cholesky chain)
         // k_chol_flow's RHS panel halves left the Gram as per-block partials (d_gblk); otherwise
         // k_border_gram forms it from the forward-solved rows
-        if (!gblk) k_border_gram<<<GRAM_SEG, 256, 0, c.stream>>>(c.d_S, ld, c.L.n_pad, c.d_bscr + 32 * 14);
+        if (!gblk) k_border_gram<<<GRAM_SEG, 256, 0, c.stream>>>(c.d_S, ld, c.L.n_pad, c.d_bscr + BSC_GRAM);
         if (flow)  // the 14 coefficients only; k_bwd_flow applies them to its block
-            k_border_combine<<<1, 256, 0, c.stream>>>(c.d_S, ld, c.L.n_pad, c.d_bscr + 32 * 14, coef,
+            k_border_combine<<<1, 256, 0, c.stream>>>(c.d_S, ld, c.L.n_pad, c.d_bscr + BSC_GRAM, coef,
                                                       gblk ? c.d_gblk : nullptr, (int)nb);
         else
             k_border_combine<<<(unsigned)((c.L.n_pad + 255) / 256), 256, 0, c.stream>>>(c.d_S, ld, c.L.n_pad,
-                                                                                       c.d_bscr + 32 * 14, nullptr, gblk ? c.d_gblk : nullptr, (int)nb);
+                                                                                       c.d_bscr + BSC_GRAM, nullptr, gblk ? c.d_gblk : nullptr, (int)nb);
     }
     if (flow) {  // one launch, every workgroup resident; roots solve by substitution
         k_bwd_flow<<<(unsigned)(nb + combine), 256, BWD_LDS, c.stream>>>(
             c.d_S, ld, c.L.n_pad, c.d_linv, c.d_dinv, c.d_X, c.d_delta, c.L.u_c, c.d_sched + s.bf_start,
             c.d_sched + s.bf_src, c.d_bflags, c.d_scal, c.set.inner_constraints ? coef : nullptr, combine,
-            c.d_bscr + 32 * 14, c.d_gblk, (int)nb, c.d_tickets + 1, s.split ? c.d_bown : nullptr,
-            s.split ? c.d_bscr + BSC_OFF : nullptr);
+            c.d_bscr + BSC_GRAM, c.d_gblk, (int)nb, c.d_tickets + 1, s.split ? c.d_bown : nullptr,
+            s.split ? c.d_bscr + BSC_SCALE : nullptr);
         FBA_HIP(hipGetLastError());
         return FBA_OK;
     }
@@ -3113,7 +3105,8 @@ int chol_setup(Ctx& c) {
     const size_t nf = c.flags_bytes / sizeof(unsigned);
     // [flags][bflags][split-target counters][update flags][3 tickets: k_chol_flow, k_bwd_flow, flow B]
     c.n_sync = (int64_t)(2 * nf + std::max(c.sched.n_counters, 1) + std::max(c.sched.n_tflags, 1) + 3);
-    FBA_HIP(hipMalloc((void**)&c.d_flags, sizeof(unsigned) * c.n_sync));
+    int rc;
+    if ((rc = dalloc(c, &c.d_flags, (size_t)c.n_sync))) return rc;
     FBA_HIP(hipMemset(c.d_flags, 0, sizeof(unsigned) * c.n_sync));
     c.d_bflags = c.d_flags + nf;
     c.d_counters = c.d_bflags + nf;

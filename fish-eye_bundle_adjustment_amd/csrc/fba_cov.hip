@@ -176,15 +176,15 @@ __global__ __launch_bounds__(64) void k_border_hinv(const double* __restrict__ g
     __shared__ double g[15][15];
     __shared__ double H[14][28];
     const int tid = threadIdx.x;
-    for (int e = tid; e < 120; e += 64) {
+    for (int e = tid; e < GRAM_N; e += 64) {
         int a = 0, rem = e;
         while (rem >= 15 - a) { rem -= 15 - a; ++a; }
         const int b = a + rem;
         double v = 0.0;
         if (gblk)
-            for (int q = 0; q < nblk; ++q) v += gblk[(int64_t)q * 256 + a * 16 + b];
+            for (int q = 0; q < nblk; ++q) v += gblk[(int64_t)q * GRAM_BLK + a * 16 + b];
         else
-            for (int q = 0; q < nseg; ++q) v += gpart[q * 120 + e];
+            for (int q = 0; q < nseg; ++q) v += gpart[q * GRAM_N + e];
         g[a][b] = g[b][a] = v;
     }
     __syncthreads();
@@ -292,10 +292,10 @@ __global__ __launch_bounds__(256) void k_cov_pts(const double* __restrict__ S, i
     if (p >= n_lp) return;
     const int o0 = lp_start[p], m = lp_start[p + 1] - o0;
     const double* P = PT + p * ps;
-    const double* Tc = P + 12 + 3 * cw;
+    const double* Tc = P + pt_tc(cw);
     const int64_t cam0 = 6 * (int64_t)n_img + (int64_t)lp_cam[p] * cw;
     auto grp_rows = [&](int g, int64_t& r0, int& n, const double*& T) {
-        if (g < m) { r0 = 6 * (int64_t)img[o0 + g]; n = 6; T = WT + (int64_t)(o0 + g) * 18; }
+        if (g < m) { r0 = 6 * (int64_t)img[o0 + g]; n = 6; T = WT + (int64_t)(o0 + g) * T_ROW; }
         else { r0 = cam0; n = cw; T = Tc; }
     };
     double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
@@ -388,10 +388,10 @@ __global__ __launch_bounds__(256) void k_cov_pts_blk(const double* __restrict__ 
     if (p >= n_lp) return;
     const int o0 = lp_start[p], m = lp_start[p + 1] - o0;
     const double* P = PT + p * ps;
-    const double* Tc = P + 12 + 3 * cw;
+    const double* Tc = P + pt_tc(cw);
     const int64_t cam0 = 6 * (int64_t)n_img + (int64_t)lp_cam[p] * cw;
     auto grp_rows = [&](int g, int64_t& r0, int& n, const double*& T) {
-        if (g < m) { r0 = 6 * (int64_t)img[o0 + g]; n = 6; T = WT + (int64_t)(o0 + g) * 18; }
+        if (g < m) { r0 = 6 * (int64_t)img[o0 + g]; n = 6; T = WT + (int64_t)(o0 + g) * T_ROW; }
         else { r0 = cam0; n = cw; T = Tc; }
     };
     double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0;
@@ -499,12 +499,12 @@ __global__ __launch_bounds__(ELL_WG) void k_ellipsoid(const double* __restrict__
     eig3_block(b, o);
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 12; ++k) sh[t * ELL_SO + k] = o[k];
+    for (int k = 0; k < ELL_OUT; ++k) sh[t * ELL_SO + k] = o[k];
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
+    for (int k = 0; k < ELL_OUT; ++k) {
         const int e = t + ELL_WG * k;
-        if (e < 12 * np) ell[12 * p0 + e] = sh[(e / 12) * ELL_SO + e % 12];
+        if (e < ELL_OUT * np) ell[ELL_OUT * p0 + e] = sh[(e / ELL_OUT) * ELL_SO + e % ELL_OUT];
     }
 }
 
@@ -540,23 +540,20 @@ int launch_selinv(Ctx& c, SelInv& si) {
 
     // the last level's diagonal-block inverses (the iteration's backward solve does without them)
     if ((rc = launch_trtri_last(c))) return rc;
-    const int nz = L.nrhs > 1 ? 14 : 0;
+    const int nz = L.nrhs > 1 ? BORDER_COLS : 0;
     double *d_Z = nullptr, *d_Wz = nullptr, *d_h = nullptr, *d_g = nullptr;
-    // scratch from the context's covariance workspace (kept across calls: no allocation per call)
-    int& next_slot = si.next_slot;
-    next_slot = 0;
-    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
-    auto cleanup = [&]() {};
+    // scratch from the context's workspace (kept across calls: no allocation per call)
     if (nz) {
-        if ((rc = alloc(&d_Z, 14 * (size_t)n_pad)) || (rc = alloc(&d_Wz, 14 * (size_t)n_pad)) ||
-            (rc = alloc(&d_h, 196)) || (rc = alloc(&d_g, 64 * 120))) { cleanup(); return rc; }
+        if ((rc = ws_get(c, WS_SEL_Z, BORDER_COLS * (size_t)n_pad, &d_Z)) ||
+            (rc = ws_get(c, WS_SEL_WZ, BORDER_COLS * (size_t)n_pad, &d_Wz)) ||
+            (rc = ws_get(c, WS_SEL_HINV, (size_t)BORDER_COLS * BORDER_COLS, &d_h)) ||
+            (rc = ws_get(c, WS_SEL_GRAM, (size_t)GRAM_SEG * GRAM_N, &d_g)))
+            return rc;
         int nseg = 0;
         // (subtree split: the Gram from the all-reduced per-block partials; another rank's columns of this
         // rank's RHS rows were never forward-solved here)
-        if ((!s_split(c) && (rc = launch_border_gram(c, d_g, &nseg))) || (rc = launch_backward_rows(c, 1, 14, d_Z))) {
-            cleanup();
+        if ((!s_split(c) && (rc = launch_border_gram(c, d_g, &nseg))) || (rc = launch_backward_rows(c, 1, BORDER_COLS, d_Z)))
             return rc;
-        }
         k_border_hinv<<<1, 64, 0, c.stream>>>(d_g, nseg, s_split(c) ? c.d_gblk : nullptr, (int)nb, d_h);
         k_border_wz<<<(unsigned)((n_pad + 255) / 256), 256, 0, c.stream>>>(d_Z, d_h, d_Wz, n_pad);
     }
@@ -579,7 +576,7 @@ int launch_selinv(Ctx& c, SelInv& si) {
     }
     double* d_Y = nullptr;
     int64_t *d_tasks = nullptr, *d_terms = nullptr;
-    if ((rc = alloc(&d_Y, ymax * CB * CB))) { cleanup(); return rc; }
+    if ((rc = ws_get(c, WS_SEL_Y, ymax * CB * CB, &d_Y))) return rc;
     // every phase's task / term lists built up front and uploaded once; the phases (three per level,
     // top level first) then run back to back on the stream, no host round trip in between
     auto blk = [&](int64_t i, int64_t j) { return i * CB * ld + j * CB; };
@@ -663,11 +660,10 @@ int launch_selinv(Ctx& c, SelInv& si) {
     }
     double* d_P = nullptr;
     int64_t *d_parts = nullptr, *d_combs = nullptr;
-    if ((rc = alloc((double**)&d_tasks, std::max<size_t>(tasks.size(), 1))) ||
-        (rc = alloc((double**)&d_terms, std::max<size_t>(terms.size(), 1))) ||
-        (rc = alloc((double**)&d_parts, std::max<size_t>(parts.size(), 1))) ||
-        (rc = alloc((double**)&d_combs, std::max<size_t>(combs.size(), 1))) ||
-        (rc = alloc(&d_P, (size_t)std::max<int64_t>(max_slots, 1) * CB * CB))) { cleanup(); return rc; }
+    if ((rc = ws_get(c, WS_SEL_TASKS, tasks.size(), &d_tasks)) || (rc = ws_get(c, WS_SEL_TERMS, terms.size(), &d_terms)) ||
+        (rc = ws_get(c, WS_SEL_PARTS, parts.size(), &d_parts)) || (rc = ws_get(c, WS_SEL_COMBS, combs.size(), &d_combs)) ||
+        (rc = ws_get(c, WS_SEL_P, (size_t)std::max<int64_t>(max_slots, 1) * CB * CB, &d_P)))
+        return rc;
     if (!tasks.empty()) {
         FBA_HIP(hipMemcpyAsync(d_tasks, tasks.data(), sizeof(int64_t) * tasks.size(), hipMemcpyHostToDevice, c.stream));
         FBA_HIP(hipMemcpyAsync(d_terms, terms.data(), sizeof(int64_t) * terms.size(), hipMemcpyHostToDevice, c.stream));
@@ -697,8 +693,6 @@ static int launch_cov_outputs(Ctx& c, SelInv& si, double* d_cdiag, double* d_pdi
     const double *d_Z = si.d_Z, *d_Wz = si.d_Wz;
     const int nz = si.nz;
     int rc;
-    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, si.next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
-    auto cleanup = [&]() {};
     if (d_cdiag)
         k_cov_cam<<<(unsigned)((L.u_c + 255) / 256), 256, 0, c.stream>>>(c.d_S, ld, d_Z, d_Wz, nz, n_pad, L.u_c, L.n_img,
                                                                          L.cw, L.nk, c.d_cam_tab, c.cam_tab_stride, d_cdiag);
@@ -707,41 +701,15 @@ static int launch_cov_outputs(Ctx& c, SelInv& si, double* d_cdiag, double* d_pdi
                                                           d_iblk);
     double* d_T = nullptr;  // T = W Vinv per tie observation, rebuilt from the records (OBS_REC)
     if (d_pdiag && c.n_lp > 0 &&
-        ((rc = alloc(&d_T, (size_t)18 * std::max<int64_t>(c.n_obs_tie, 1))) || (rc = launch_obs_T(c, d_T)))) {
-        cleanup();
+        ((rc = ws_get(c, WS_OBS_T, (size_t)T_ROW * std::max<int64_t>(c.n_obs_tie, 1), &d_T)) || (rc = launch_obs_T(c, d_T))))
         return rc;
-    }
     if (d_pdiag && c.n_lp > 0)
         k_cov_pts<<<(unsigned)((c.n_lp + 3) / 4), 256, 0, c.stream>>>(c.d_S, ld, d_Z, d_Wz, nz, n_pad, d_T, c.d_pt_tab,
                                                                       c.pt_comp, c.d_lp_start, c.d_lp_tie, c.d_lp_cam,
                                                                       c.d_img, c.n_lp, L.n_img, L.cw, L.u_c, d_pdiag);
     FBA_HIP(hipGetLastError());
-    if (d_pdiag && (rc = launch_gen_cov(c, d_Z, d_Wz, nz, d_pdiag))) { cleanup(); return rc; }
+    if (d_pdiag && (rc = launch_gen_cov(c, d_Z, d_Wz, nz, d_pdiag))) return rc;
     si.d_T = d_T;
-    return FBA_OK;
-}
-
-int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
-                      const int32_t* d_icam, int n_iblk) {
-    SelInv si;
-    int rc;
-    if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)))
-        return rc;
-    FBA_HIP(hipStreamSynchronize(c.stream));
-    c.have_factor = false;
-    return FBA_OK;
-}
-
-// fba_reliability: fba_covariance's launches, then the reliability kernels on the same selected inverse
-int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
-                       const int32_t* d_icam, int n_iblk, double* d_q, double* d_red, double* d_wst) {
-    SelInv si;
-    int rc;
-    if ((rc = launch_selinv(c, si)) || (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, d_iblk, d_islot, d_icam, n_iblk)) ||
-        (rc = launch_rel_outputs(c, si, d_q, d_red, d_wst)))
-        return rc;
-    FBA_HIP(hipStreamSynchronize(c.stream));
-    c.have_factor = false;
     return FBA_OK;
 }
 
@@ -751,10 +719,9 @@ int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk,
 static int launch_blk_outputs(Ctx& c, SelInv& si, double sigma02, double* d_blk, double* d_ell) {
     const Layout& L = c.L;
     int rc;
-    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, si.next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
-    FBA_HIP(hipMemsetAsync(d_blk, 0, sizeof(double) * 6 * (size_t)std::max(L.n_tie, 1), c.stream));
+    FBA_HIP(hipMemsetAsync(d_blk, 0, sizeof(double) * TIE_BLK * (size_t)std::max(L.n_tie, 1), c.stream));
     if (c.n_lp > 0) {
-        if (!si.d_T && ((rc = alloc(&si.d_T, (size_t)18 * std::max<int64_t>(c.n_obs_tie, 1))) || (rc = launch_obs_T(c, si.d_T))))
+        if (!si.d_T && ((rc = ws_get(c, WS_OBS_T, (size_t)T_ROW * std::max<int64_t>(c.n_obs_tie, 1), &si.d_T)) || (rc = launch_obs_T(c, si.d_T))))
             return rc;
         k_cov_pts_blk<<<(unsigned)((c.n_lp + 3) / 4), 256, 0, c.stream>>>(c.d_S, L.ld, si.d_Z, si.d_Wz, si.nz, L.n_pad, si.d_T,
                                                                           c.d_pt_tab, c.pt_comp, c.d_lp_start, c.d_lp_tie,
@@ -770,9 +737,9 @@ static int launch_blk_outputs(Ctx& c, SelInv& si, double sigma02, double* d_blk,
     return FBA_OK;
 }
 
-// fba_postfit_outputs: fba_covariance's launches, the reliability kernels when d_red is given (then d_q and d_wst
-// too), the block kernels and k_ellipsoid when d_blk / d_ell are given (d_ell needs d_blk), all on one selected
-// inverse
+// the post-fit driver of fba_covariance, fba_reliability and fba_postfit_outputs: the covariance launches, the
+// reliability kernels when d_red is given (then d_q and d_wst too), the block kernels and k_ellipsoid when d_blk /
+// d_ell are given (d_ell needs d_blk), all on one selected inverse
 int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot, const int32_t* d_icam,
                    int n_iblk, double* d_q, double* d_red, double* d_wst, double sigma02, double* d_blk, double* d_ell) {
     SelInv si;

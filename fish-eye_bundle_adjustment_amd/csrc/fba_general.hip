@@ -29,16 +29,7 @@
 namespace fba {
 
 template <int NK>
-struct GL {
-    static constexpr int CW = 5 + NK, NJ = 9 + CW, JS = 2 * NJ + 2;
-    static constexpr int NIMG = 27 + 6 * CW;           // image partial (LR<NK>::NIMG)
-    static constexpr int NPK = CW * (CW + 1) / 2;
-    static constexpr int NCAM = NPK + CW;              // camera partial (LR<NK>::NCAM)
-    static constexpr int NX = 6 * CW, NKK = CW * CW;
-    static constexpr int GC = 6 * CW;                  // gpc table: Uc 3CW | Tc 3CW
-};
-constexpr int GPT = 18;  // point table: Vinv 6 | R 6 | rb 3 | vb 3
-constexpr int GUG = 36;  // gimg table: Ug 18 | T 18
+struct GL : LayNK<NK> {};  // (GPT, GUG and the rest: fba_layout.h)
 
 // fixed xor-butterfly sum over the 64 lanes of a wave (every lane gets the sum)
 __device__ __forceinline__ double wave_sum(double v) {
@@ -158,9 +149,9 @@ __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, 
     }
     // per image of the point: Ug = sum_o W_o R, T = sum_o W_o V^-1 over its observations there
     for (int gi = A[g.g_gi + q] + l; gi < A[g.g_gi + q + 1]; gi += 64) {
-        double u[18], t[18];
+        double u[T_ROW], t[T_ROW];
 #pragma unroll
-        for (int m = 0; m < 18; ++m) u[m] = t[m] = 0.0;
+        for (int m = 0; m < T_ROW; ++m) u[m] = t[m] = 0.0;
         for (int o = A[g.gi_obs + gi]; o < A[g.gi_obs + gi + 1]; ++o) {
             const double* Jo = J + (int64_t)o * JS;
             const double px0 = Jo[6 + CW], px1 = Jo[7 + CW], px2 = Jo[8 + CW];
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(64) void k_gen_point(const double* __restrict__ J, 
         }
         double* out = gug + (int64_t)gi * GUG;
 #pragma unroll
-        for (int m = 0; m < 18; ++m) { out[m] = u[m]; out[18 + m] = t[m]; }
+        for (int m = 0; m < T_ROW; ++m) { out[m] = u[m]; out[GUG_T + m] = t[m]; }
     }
 }
 
@@ -198,15 +189,15 @@ __global__ __launch_bounds__(256) void k_gen_keys(const double* __restrict__ J, 
     int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     auto dot3 = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
     // pair keys: value 6 a + b = -Ug1[a] . Ug2[b] (a: row of the higher image, as k_lin_reduce)
-    if (t < g.n_gpk * 36) {
-        const int64_t k = t / 36;
-        const int v = (int)(t % 36), a = v / 6, b = v % 6;
+    if (t < g.n_gpk * PAIR_BLK) {
+        const int64_t k = t / PAIR_BLK;
+        const int v = (int)(t % PAIR_BLK), a = v / 6, b = v % 6;
         const double* u1 = gug + (int64_t)A[g.gpk + 2 * k] * GUG;
         const double* u2 = gug + (int64_t)A[g.gpk + 2 * k + 1] * GUG;
-        ppart[(int64_t)A[g.pk_slot + g.pk0 + k] * 36 + v] = -dot3(u1 + 3 * a, u2 + 3 * b);
+        ppart[(int64_t)A[g.pk_slot + g.pk0 + k] * PAIR_BLK + v] = -dot3(u1 + 3 * a, u2 + 3 * b);
         return;
     }
-    t -= g.n_gpk * 36;
+    t -= g.n_gpk * PAIR_BLK;
     if (t < g.n_gi * NIMG) {
         const int64_t gi = t / NIMG;
         const int v = (int)(t % NIMG);
@@ -221,15 +212,15 @@ __global__ __launch_bounds__(256) void k_gen_keys(const double* __restrict__ J, 
                 s += px * Jo[a] * Jo[b] + py * Jo[NJ + a] * Jo[NJ + b];
             }
             r = dot3(ug + 3 * a, ug + 3 * b);
-        } else if (v < 27) {  // right-hand side
+        } else if (v < IMG_PART_CAM) {  // right-hand side
             const int a = v - 21;
             for (int o = o0; o < o1; ++o) {
                 const double* Jo = J + (int64_t)o * JS;
                 s += px * Jo[a] * Jo[2 * NJ] + py * Jo[NJ + a] * Jo[2 * NJ + 1];
             }
             r = dot3(ug + 3 * a, gpt + (int64_t)A[g.gi_gp + gi] * GPT + 12);
-        } else {  // own camera: 27 + 6 b + a (camera column b, image row a)
-            const int a = (v - 27) % 6, b = (v - 27) / 6;
+        } else {  // own camera: IMG_PART_CAM + 6 b + a (camera column b, image row a)
+            const int a = (v - IMG_PART_CAM) % 6, b = (v - IMG_PART_CAM) / 6;
             for (int o = o0; o < o1; ++o) {
                 const double* Jo = J + (int64_t)o * JS;
                 s += px * Jo[6 + b] * Jo[a] + py * Jo[NJ + 6 + b] * Jo[NJ + a];
@@ -326,7 +317,7 @@ __global__ __launch_bounds__(256) void k_gen_backsub(const int32_t* __restrict__
     const double* P = gpt + q * GPT;
     double d0 = P[15], d1 = P[16], d2 = P[17];
     for (int gi = A[g.g_gi + q]; gi < A[g.g_gi + q + 1]; ++gi) {
-        const double* T = gug + (int64_t)gi * GUG + 18;
+        const double* T = gug + (int64_t)gi * GUG + GUG_T;
         const double* de = delta + 6 * (int64_t)A[g.gi_img + gi];
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
@@ -363,7 +354,7 @@ __global__ __launch_bounds__(256) void k_cov_gen(const double* __restrict__ S, i
     const int i0 = A[g.g_gi + q], ni = A[g.g_gi + q + 1] - i0;
     const int c0 = A[g.g_gc + q], nc = A[g.g_gc + q + 1] - c0;
     auto grp = [&](int x, int64_t& r0, int& n, const double*& T) {
-        if (x < ni) { r0 = 6 * (int64_t)A[g.gi_img + i0 + x]; n = 6; T = gug + (int64_t)(i0 + x) * GUG + 18; }
+        if (x < ni) { r0 = 6 * (int64_t)A[g.gi_img + i0 + x]; n = 6; T = gug + (int64_t)(i0 + x) * GUG + GUG_T; }
         else { r0 = 6 * (int64_t)n_img + (int64_t)A[g.gc_cam + c0 + x - ni] * CW; n = CW; T = gcu + (int64_t)(c0 + x - ni) * GC + 3 * CW; }
     };
     const int ng = ni + nc;
@@ -431,7 +422,7 @@ __global__ __launch_bounds__(256) void k_cov_gen_blk(const double* __restrict__ 
     const int i0 = A[g.g_gi + q], ni = A[g.g_gi + q + 1] - i0;
     const int c0 = A[g.g_gc + q], nc = A[g.g_gc + q + 1] - c0;
     auto grp = [&](int x, int64_t& r0, int& n, const double*& T) {
-        if (x < ni) { r0 = 6 * (int64_t)A[g.gi_img + i0 + x]; n = 6; T = gug + (int64_t)(i0 + x) * GUG + 18; }
+        if (x < ni) { r0 = 6 * (int64_t)A[g.gi_img + i0 + x]; n = 6; T = gug + (int64_t)(i0 + x) * GUG + GUG_T; }
         else { r0 = 6 * (int64_t)n_img + (int64_t)A[g.gc_cam + c0 + x - ni] * CW; n = CW; T = gcu + (int64_t)(c0 + x - ni) * GC + 3 * CW; }
     };
     const int ng = ni + nc;
@@ -538,7 +529,7 @@ int launch_gen_keys(Ctx& c) {
 #define GK(NKV)                                                                                                       \
     {                                                                                                                 \
         using Q = GL<NKV>;                                                                                            \
-        const int64_t n = g.n_gpk * 36 + g.n_gi * Q::NIMG + g.n_gx * Q::NX + g.n_gc * Q::NCAM + g.n_gkk * Q::NKK;     \
+        const int64_t n = g.n_gpk * PAIR_BLK + g.n_gi * Q::NIMG + g.n_gx * Q::NX + g.n_gc * Q::NCAM + g.n_gkk * Q::NKK;     \
         k_gen_keys<NKV><<<grid_of(n, 256), 256, 0, c.stream>>>(c.d_J, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, c.d_ppart, \
                                                                c.d_ipart, c.d_cpart, c.d_xpart, c.d_kpart, px, py);  \
     }

@@ -8,45 +8,29 @@
 // at the ABI boundary through the index maps below.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <vector>
 
 #include "../../include/fba.h"
+#include "fba_layout.h"
 
 namespace fba {
 
 constexpr int NB = 128;       // Cholesky block size (rows/cols of one panel block, fba_chol.hip)
-constexpr int PTRACE_WG = 2048;  // FBA_PANEL_TRACE: workgroup slots per level
-constexpr int FTRACE = 56;       // FBA_PANEL_TRACE: stamps per k_chol_flow record ([48]: its workgroup's start)
 // k_chol_flow: a fused diagonal update's tiles of tile columns >= FLOW_CSPLIT go to a helper record,
 // added into the potrf's LDS block during its bulk step FLOW_CSPLIT - 2 (fba_order.cpp build_flow)
 constexpr int FLOW_CSPLIT = 3;
 // k_bwd_flow's "not yet published" value of the solution blocks X (a signalling NaN with a payload no
 // arithmetic produces): the consumers poll the data itself, k_border_rhs resets it every solve
 constexpr uint64_t X_SENTINEL = 0x7FF4DEADBEEF5A5Aull;
-constexpr int SCAL_SPINS = 6;  // d_scal slot: this context's hand-off poll bound (fba_chol.hip spin_expired)
-// the value stored there for a requested bound: <= 0 means the default 1 << 22 (~0.3 s), and a bound is
-// clamped to 2^32 - 1 (spin_expired compares it with a 32-bit counter)
+// the value stored in d_scal[SCAL_SPINS] for a requested bound: <= 0 means the default 1 << 22 (~0.3 s), and a
+// bound is clamped to 2^32 - 1 (spin_expired compares it with a 32-bit counter)
 inline double spin_bound_value(long long spins) {
     return spins <= 0 ? (double)(1u << 22) : (double)(spins < 0xffffffffLL ? spins : 0xffffffffLL);
 }
-constexpr int SCAL_DAMP = 7;   // d_scal slot: the Levenberg-Marquardt damping parameter lambda (fba_set_damping; 0: off)
-constexpr int CHUNK_OBS = 256;  // observations per k_lin_reduce / k_lin_point workgroup (chunk)
-constexpr int LR_PROF = 10;     // FBA_LR_PROFILE: 64-bit words per chunk (k_lin_reduce's stamps, fba_capi.cpp's print)
-// tie points per chunk and co-visibility terms per chunk staged in LDS (a single larger point's are
-// read from HBM instead): smaller for nK >= 6, whose wider Jacobian rows leave less of the 160 KiB LDS
-// (k_lin_reduce's LR<NK>::LDS, static_assert there); the host chunking uses the same numbers
-constexpr int chunk_pts(int nk) { return nk <= 5 ? 64 : 32; }
-constexpr int chunk_terms(int nk) { return nk <= 5 ? 2048 : 1024; }
-
-// per-image device table (k_params): eop[6], M[9], dM/domega[9], dM/dphi[9], dM/dkappa[9], pad
-constexpr int IMG_TAB = 48;
-// per-camera device table: xp yp c ydir P1 P2 rmax2 pad, K[nK], scale[nK] (rmax^(2j))
-constexpr int CAM_TAB_HDR = 8;
-// d_bscr: [32][14] k_border_weights segments | [16][120] Gram segments | [16] combine coefficients |
-// [16] the subtree split's B-row scales sqrt(W_d)
-constexpr int BSC_OFF = 32 * 14 + 16 * 120 + 16;
 
 struct Layout {
     int n_img = 0, n_cam = 0, n_tie = 0, nk = 1, cw = 6;  // n_img: internal image slots (padding included)
@@ -204,6 +188,24 @@ struct Whiten {
     double k = 0.0;
 };
 
+// Workspace slots (ws_get): one name per purpose, so no two users share a buffer by accident.
+enum WsSlot : int {
+    // launch_selinv (fba_cov.hip): the border's Z and Wz, H^-1, the Gram segments, Y, the task / term / part /
+    // combine lists and the split partials
+    WS_SEL_Z, WS_SEL_WZ, WS_SEL_HINV, WS_SEL_GRAM, WS_SEL_Y, WS_SEL_TASKS, WS_SEL_TERMS, WS_SEL_PARTS, WS_SEL_COMBS, WS_SEL_P,
+    WS_SEL_END,             // one past launch_selinv's range
+    WS_OBS_T = WS_SEL_END,  // T = W Vinv per tie observation (launch_cov_outputs, launch_rel_outputs, launch_blk_outputs)
+    WS_REL_XG,              // k_rel_gen's X rows
+    // the post-fit outputs (covariance_impl)
+    WS_CDIAG, WS_PDIAG, WS_IBLK, WS_ISLOT, WS_ICAM, WS_REL_Q, WS_REL_RED, WS_REL_WST, WS_TIE_BLK, WS_ELLIPSOID,
+    WS_WEIGHTS,             // fba_set_weights / fba_get_weights staging, PHO order
+    WS_COST,                // fba_cost: [4] sums, then the block partials
+    WS_LM_SAVE,             // fba_adjust_lm: xhat before a trial
+    WS_RAY, WS_RAY_ST, WS_RAY_XU, WS_ISECT_OUT, WS_ISECT_ST,  // fba_image_rays / fba_intersect
+    WS_COUNT
+};
+static_assert(WS_SEL_END - WS_SEL_Z == 10 && WS_OBS_T >= WS_SEL_END, "launch_selinv's slots run into the next name");
+
 struct Ctx {
     fba_problem prob{};   // shallow copy (pointers valid only during fba_create)
     fba_settings set{};
@@ -212,7 +214,7 @@ struct Ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     // the two halves of an iteration captured once as HIP graphs (a capturable stream, no timing /
-    // probe / profile events; FBA_NO_GRAPH=1 disables): [0] linearise + accumulate, [1] solve + update
+    // probe / profile events): [0] linearise + accumulate, [1] solve + update
     hipGraphExec_t graph[2] = {nullptr, nullptr};
     bool graphs_ok = true;
     int device = 0;
@@ -247,21 +249,21 @@ struct Ctx {
                                      // linearised by k_lin_point only]
     int64_t n_chunks_lr = 0;         // k_lin_reduce workgroups (regular + control chunks)
     GenPlan gen;                     // general tie points (fba_general.hip)
-    double* d_gpt = nullptr;         // [n_gp][18] Vinv 6 | R 6 | rb 3 | vb 3
-    double* d_gcu = nullptr;         // [n_gc][6 cw] Uc 3cw | Tc 3cw
-    double* d_gug = nullptr;         // [n_gi][36] Ug 18 | sum of T_o 18
-    double* d_xpart = nullptr;       // [n_gx][6 cw] foreign-camera partials
-    double* d_kpart = nullptr;       // [n_gkk][cw cw] camera-pair partials
+    double* d_gpt = nullptr;         // [n_gp][GPT] Vinv 6 | R 6 | rb 3 | vb 3
+    double* d_gcu = nullptr;         // [n_gc][gpc_tab(cw)] Uc 3cw | Tc 3cw
+    double* d_gug = nullptr;         // [n_gi][GUG] Ug | sum of T_o at GUG_T
+    double* d_xpart = nullptr;       // [n_gx][xcam_part(cw)] foreign-camera partials
+    double* d_kpart = nullptr;       // [n_gkk][campair_part(cw)] camera-pair partials
     AccPlan acc;                     // accumulation plan (offsets into d_acc)
     int32_t* d_acc = nullptr;
-    double* d_ppart = nullptr;       // [acc.n_pk][36] pair-block partials
-    double* d_U = nullptr;           // [n_obs_pad][18] U = W R of the observations of U-row chunks (acc.ck_tm)
+    double* d_ppart = nullptr;       // [acc.n_pk][PAIR_BLK] pair-block partials
+    double* d_U = nullptr;           // [n_obs_pad][T_ROW] U = W R of the observations of U-row chunks (acc.ck_tm)
     int ik_lanes = 8;                // k_lin_reduce's lanes per image-key unit (4: keys of <= 2 observations)
     int lr_order = 0;                // FBA_LR_ORDER at creation: the order of k_lin_reduce's (D) task queue (0: default)
-    double* d_ipart = nullptr;       // [acc.n_ik][27 + 6 cw] image partials: diagonal block, RHS, image-camera
+    double* d_ipart = nullptr;       // [acc.n_ik][img_part(cw)] image partials: diagonal block, RHS, image-camera
     uint64_t* d_lrprof = nullptr;    // FBA_LR_PROFILE: k_lin_reduce phase timestamps [n_chunks][LR_PROF]
     uint64_t* d_ptrace = nullptr;    // FBA_PANEL_TRACE: k_panel workgroup timestamps [level][PTRACE_WG][8]
-    double* d_cpart = nullptr;       // [n_chunks][cw(cw+1)/2 + cw] camera-block partials
+    double* d_cpart = nullptr;       // [n_chunks_lr + n_gc][cam_part(cw)] camera-block partials
     int32_t* d_chunk_obs = nullptr;  // [n_chunks+1] observation range of each chunk
     int32_t* d_chunk_pt = nullptr;   // [n_chunks+1] local point range of each chunk
     int64_t n_pairs = 0, n_pair_terms = 0;
@@ -291,17 +293,17 @@ struct Ctx {
     double* d_xlin = nullptr;    // [u_full] the last linearisation point (residuals after the loop)
     double* d_delta = nullptr;   // [u_full] last de-scaled correction
     double* d_img_tab = nullptr; // [n_img*IMG_TAB]
-    double* d_cam_tab = nullptr; // [n_cam*cam_tab_stride]
+    double* d_cam_tab = nullptr; // [n_cam*cam_tab_stride], cam_tab_stride = cam_tab_row(cw)
     int cam_tab_stride = 0;
-    double* d_G = nullptr;       // [n_img*42] inner-constraint blocks (6x7 per image, row-major)
-    double* d_J = nullptr;       // [n_obs_pad][ncomp] per-obs Jacobian rows + misclosure (obs-major)
+    double* d_G = nullptr;       // [n_img][G_BLK] inner-constraint blocks (6 rows of G_ROW per image)
+    double* d_J = nullptr;       // [n_obs_pad][ncomp] per-obs Jacobian rows + misclosure (obs-major), ncomp = jac_stride(cw)
     int ncomp = 0;
-    double* d_cseg = nullptr;    // [n_cam][64][NCAM] camera segment sums (k_red_cam_seg)
-    double* d_bscr = nullptr;    // border scratch: [32][14] weight segment sums | [16][120] Gram segments
-    double* d_gblk = nullptr;    // [n_pad / NB][16][16] per-column-block Gram partials of the forward-solved
+    double* d_cseg = nullptr;    // [n_cam][CAM_SEG][cam_part(cw)] camera segment sums (k_red_cam_seg)
+    double* d_bscr = nullptr;    // border scratch [BSC_TOTAL]: BSC_WSEG | BSC_GRAM | BSC_COEF | BSC_SCALE
+    double* d_gblk = nullptr;    // [n_pad / NB][GRAM_BLK] per-column-block Gram partials of the forward-solved
                                  // RHS rows (k_chol_flow; inner constraints)
-    double* d_WT = nullptr;      // [n_obs_pad][12] per-obs record: Jp and the EOP rotation columns (OBS_REC)
-    double* d_pt_tab = nullptr;  // [n_lp_pad][pt_comp] Vinv(6) vb(3) b(3) Wc(3cw) Tc(3cw)
+    double* d_WT = nullptr;      // [n_obs_pad][OBS_REC] per-obs record: Jp and the EOP rotation columns
+    double* d_pt_tab = nullptr;  // [n_lp_pad][pt_comp] PT_VINV PT_VB PT_B PT_WC pt_tc(cw), pt_comp = pt_stride(cw)
     int pt_comp = 0;
     int64_t n_lp_pad = 0;
     double* d_P = nullptr;       // [Sched::n_scratch][64*64] partial sums of split update targets
@@ -312,23 +314,19 @@ struct Ctx {
     unsigned* d_tickets = nullptr;  // [2] start-order tickets of k_chol_flow / k_bwd_flow records
     int64_t n_sync = 0;           // unsigned words of flags + bflags + counters (one allocation at d_flags,
                                   // zeroed by k_border_rhs ahead of every factorisation)
-    bool bwd_flow = true;
-    bool merge_updates = true;      // a level's trailing updates inside the next level's k_panel
-                                    // (FBA_MERGE_UPDATES=0: their own k_syrk_multi launch)
+    bool bwd_flow = true;           // one-launch backward solve (FBA_BWD_LEVELS=1: one launch per level)
     bool chol_flow = true;          // the factorisation as one persistent k_chol_flow launch (FBA_CHOL_FLOW=0:
                                     // one k_panel launch per elimination-tree level)
-    bool panel_progressive = true;  // k_panel: panel solves step with the potrf's published column blocks
-                                    // (FBA_PANEL_PROGRESSIVE=0: wait for the whole factor)         // one-launch backward solve (FBA_BWD_LEVELS=1: one launch per level)
     size_t flags_bytes = 0;
     int n_cu = 0;                // compute units (k_panel needs its whole grid resident)
     double* d_S = nullptr;       // [(n_pad+NB)*ld] normal matrix (lower) + RHS rows
     double* d_X = nullptr;       // [n_pad] solution of the bordered solve
     double* d_dinv = nullptr;    // [(n_pad/NB)*8*256] inverses of the 16x16 diagonal blocks of L
     double* d_linv = nullptr;    // [(n_pad/NB)*128*128] inverses of the 128x128 diagonal blocks of L
-    double* d_scal = nullptr;    // scalars: [1] Cholesky failure flag, [2] sumabs, [8..14] border weights
+    double* d_scal = nullptr;    // [SCAL_TOTAL] scalars of a solve (the SCAL_* slots of fba_layout.h)
     double* d_part = nullptr;    // block partial sums
     int n_part = 0;
-    double* d_res = nullptr;     // [7*n_obs] v (2) + rsd (5)
+    double* d_res = nullptr;     // [RES_ROW*n_obs] v (2 n_obs), then rsd (RSD_ROW n_obs)
     double* d_caminfo = nullptr; // [5*n_cam]
     uint8_t* d_active = nullptr; // [n_pad] 1 = estimated camera-side parameter
     uint8_t* d_counted = nullptr;// [u_full] 1 = counted in this rank's sumabs share
@@ -357,9 +355,9 @@ struct Ctx {
     double* d_pr_val = nullptr;      // [n_pres][2] p, l
     double* d_pr_out = nullptr;      // [n_prior + 1] residuals in the caller's order, then this rank's sum p v^2
     double* d_pr_part = nullptr;     // [ceil(n_pres / 256)] block partials of p v^2
-    double* h_pinned = nullptr;  // pinned host scratch (coherent, mapped: k_sum_parts writes scal[0..3] here,
-                                 // then [4] = its running count of solves, scal[5])
-    double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[4])
+    double* h_pinned = nullptr;  // [HPIN_TOTAL] pinned host scratch (coherent, mapped: k_sum_parts mirrors the d_scal
+                                 // slots below SCAL_MIRROR here, then HPIN_SEQ = its running count of solves)
+    double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[HPIN_SEQ])
     int64_t solves_enqueued = 0; // solves enqueued on the stream (k_sum_parts' count once they are done)
     double* d_hpinned = nullptr; // its device address
 
@@ -381,7 +379,9 @@ struct Ctx {
     double probe_flops = 0.0;
     hipEvent_t ev[9] = {};
     double last_ms[8] = {0};
-    std::vector<std::pair<void*, size_t>> ws;  // reusable device scratch (fba_covariance), by slot
+    // device memory of the context's lifetime: every dalloc / upload (pointer, pinned), freed by fba_destroy
+    std::vector<std::pair<void*, bool>> owned;
+    std::array<std::pair<void*, size_t>, WS_COUNT> ws{};  // reusable device scratch (ws_get), by WsSlot
 };
 
 
@@ -397,19 +397,82 @@ void set_error(const std::string& msg);
         }                                                                              \
     } while (0)
 
-// device scratch slot `slot` of at least `bytes` (grown when needed, kept until fba_destroy)
-inline int ws_get(Ctx& c, int slot, size_t bytes, void** p) {
-    if ((int)c.ws.size() <= slot) c.ws.resize(slot + 1, {nullptr, 0});
-    auto& e = c.ws[slot];
-    if (e.second < bytes) {
-        if (e.first) (void)hipFree(e.first);
-        e = {nullptr, 0};
-        if (hipMalloc(&e.first, bytes) != hipSuccess) { set_error("hipMalloc failed (workspace)"); return FBA_ERR_HIP; }
-        e.second = bytes;
-    }
-    *p = e.first;
+// ---- device memory: three lifetimes, one mechanism each ----
+// Every device and pinned allocation of the library passes through mem_alloc / mem_free, which keep the
+// process-wide count of live allocations (fba_test_live_allocations).
+inline std::atomic<int64_t> g_live_allocations{0};
+inline hipError_t mem_alloc(void** p, size_t bytes, bool pinned = false) {
+    const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocMapped | hipHostMallocCoherent) : hipMalloc(p, bytes);
+    if (e == hipSuccess) g_live_allocations.fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+inline void mem_free(void* p, bool pinned = false) {
+    if (!p) return;
+    (void)(pinned ? hipHostFree(p) : hipFree(p));
+    g_live_allocations.fetch_sub(1, std::memory_order_relaxed);
+}
+
+// context lifetime: n elements (at least one) recorded in c.owned, freed by fba_destroy and by nothing else
+template <typename T>
+int dalloc(Ctx& c, T** p, size_t n, bool pinned = false) {
+    void* q = nullptr;
+    FBA_HIP(mem_alloc(&q, (n ? n : 1) * sizeof(T), pinned));
+    c.owned.emplace_back(q, pinned);
+    *p = static_cast<T*>(q);
     return FBA_OK;
 }
+template <typename T>
+int upload(Ctx& c, T** p, const std::vector<T>& v) {
+    int rc = dalloc(c, p, v.size());
+    if (rc) return rc;
+    if (!v.empty()) FBA_HIP(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return FBA_OK;
+}
+
+// workspace: slot `slot` with room for n elements (at least one); grown when needed, kept until fba_destroy
+template <typename T>
+int ws_get(Ctx& c, WsSlot slot, size_t n, T** p) {
+    auto& e = c.ws[slot];
+    const size_t bytes = (n ? n : 1) * sizeof(T);
+    if (e.second < bytes) {
+        mem_free(e.first);
+        e = {nullptr, 0};
+        FBA_HIP(mem_alloc(&e.first, bytes));
+        e.second = bytes;
+    }
+    *p = static_cast<T*>(e.first);
+    return FBA_OK;
+}
+
+// call lifetime: a device buffer freed when the handle goes out of scope (move-only)
+template <typename T>
+class DevBuf {
+    T* p_ = nullptr;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { mem_free(p_); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { mem_free(p_); }
+    T* get() const { return p_; }
+    int alloc(size_t n) {
+        mem_free(p_);
+        p_ = nullptr;
+        FBA_HIP(mem_alloc((void**)&p_, (n ? n : 1) * sizeof(T)));
+        return FBA_OK;
+    }
+    int upload(const std::vector<T>& v) {
+        int rc = alloc(v.size());
+        if (rc) return rc;
+        if (!v.empty()) FBA_HIP(hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return FBA_OK;
+    }
+};
 
 // host planning (fba_order.cpp, fba_plan.cpp: no HIP call, they link without the HIP runtime)
 std::vector<int32_t> camera_order(const fba_problem* p);  // internal image slot -> EXT row or -1 (fba_order.cpp)
@@ -473,21 +536,18 @@ int launch_residuals(Ctx& c);    // v per obs, partial sums
 int launch_set_weights(Ctx& c, const double* d_wpho);   // d_sw[local] = sqrt(d_wpho[PHO])
 int launch_get_weights(Ctx& c, double* d_wpho);         // d_wpho[PHO] = d_weff[local] (own rows only)
 int launch_build_rsd(Ctx& c, const double* d_v, const double* d_xpyp, double* d_rsd);  // BuildRSD for a given v
-int launch_covariance(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
-                      const int32_t* d_icam, int n_iblk);  // post-fit covariance (fba_cov.hip)
 // what the selected inverse leaves for the kernels reading it (fba_cov.hip launch_selinv): the border's Z and
-// Wz ([14][n_pad], nullptr with nz = 0), the per-observation T table once built, the next free workspace slot
+// Wz ([BORDER_COLS][n_pad], nullptr with nz = 0), the per-observation T table once built (WS_OBS_T)
 struct SelInv {
     double *d_Z = nullptr, *d_Wz = nullptr, *d_T = nullptr;
-    int nz = 0, next_slot = 0;
+    int nz = 0;
 };
 int launch_selinv(Ctx& c, SelInv& si);
 int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst);  // fba_rel.hip
-int launch_reliability(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot,
-                       const int32_t* d_icam, int n_iblk, double* d_q, double* d_red, double* d_wst);
-// fba_postfit_outputs (fba_cov.hip): the two drivers above on one selected inverse, plus the tie points' full
-// 3 x 3 blocks sigma02 Cx_pp (d_blk [6 n_tie]; k_cov_pts_blk, k_cov_gen_blk) and their ellipsoids (d_ell [12 n_tie];
-// k_ellipsoid); d_red == nullptr: no reliability, d_blk == nullptr: no blocks (then no d_ell either)
+// the post-fit driver (fba_cov.hip) of fba_covariance, fba_reliability and fba_postfit_outputs: the covariance and
+// the reliability outputs on one selected inverse, plus the tie points' full 3 x 3 blocks sigma02 Cx_pp (d_blk
+// [TIE_BLK n_tie]; k_cov_pts_blk, k_cov_gen_blk) and their ellipsoids (d_ell [ELL_OUT n_tie]; k_ellipsoid);
+// d_red == nullptr: no reliability, d_blk == nullptr: no blocks (then no d_ell either)
 int launch_gen_cov_blk(Ctx& c, const double* Z, const double* Wz, int nz, double sigma02, double* blk);
 int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, const int32_t* d_islot, const int32_t* d_icam,
                    int n_iblk, double* d_q, double* d_red, double* d_wst, double sigma02, double* d_blk, double* d_ell);

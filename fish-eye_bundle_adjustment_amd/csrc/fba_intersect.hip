@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_rays(const double* __restrict__ xy, con
     const int st = ray_unproject<NK>(xyv.x, xyv.y, ct[0], ct[1], ct[2], ct[3], ct[4], ct[5], ct + CAM_TAB_HDR, NK, type,
                                      xu, yu, c0, c1, c2);
     const double* M = it + 6;  // d_obj = M' d_cam
-    double2* r = reinterpret_cast<double2*>(ray + 6 * o);
+    double2* r = reinterpret_cast<double2*>(ray + RAY_REC * o);
     r[0] = double2{it[0], it[1]};
     r[1] = double2{it[2], M[0] * c0 + M[3] * c1 + M[6] * c2};
     r[2] = double2{M[1] * c0 + M[4] * c1 + M[7] * c2, M[2] * c0 + M[5] * c1 + M[8] * c2};
@@ -74,7 +74,7 @@ __device__ __forceinline__ void isect_eval(int lane, int o0, int o1, const doubl
     double V00 = 0, V01 = 0, V02 = 0, V11 = 0, V12 = 0, V22 = 0, g0 = 0, g1 = 0, g2 = 0, ssq = 0, dsum = 0;
     for (int i = o0 + lane; i < o1; i += IS_LANES) {
         if (rst[i] != FBA_RAY_OK) continue;
-        const double* r = ray + 6 * (int64_t)i;
+        const double* r = ray + RAY_REC * (int64_t)i;
         const double* ct = cam_tab + (int64_t)cam[i] * cam_stride;
         const double2 u = *reinterpret_cast<const double2*>(xuo + 2 * (int64_t)i);
         const double e0 = X0 - r[0], e1 = X1 - r[1], e2 = X2 - r[2];
@@ -131,11 +131,11 @@ __global__ __launch_bounds__(256) void k_intersect(
     int status = FBA_ISECT_FEW;
     if (o1 > o0) {
         // (a) the linear solution, relative to the first ray's centre
-        const double C0 = ray[6 * (int64_t)o0], C1 = ray[6 * (int64_t)o0 + 1], C2 = ray[6 * (int64_t)o0 + 2];
+        const double C0 = ray[RAY_REC * (int64_t)o0], C1 = ray[RAY_REC * (int64_t)o0 + 1], C2 = ray[RAY_REC * (int64_t)o0 + 2];
         double A00 = 0, A01 = 0, A02 = 0, A11 = 0, A12 = 0, A22 = 0, b0 = 0, b1 = 0, b2 = 0, cnt = 0;
         for (int i = o0 + lane; i < o1; i += IS_LANES) {
             if (rst[i] != FBA_RAY_OK) continue;
-            const double* r = ray + 6 * (int64_t)i;
+            const double* r = ray + RAY_REC * (int64_t)i;
             const double d0 = r[3], d1 = r[4], d2 = r[5];
             const double m00 = 1.0 - d0 * d0, m01 = -d0 * d1, m02 = -d0 * d2, m11 = 1.0 - d1 * d1, m12 = -d1 * d2,
                          m22 = 1.0 - d2 * d2;

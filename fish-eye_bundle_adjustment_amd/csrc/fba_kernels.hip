@@ -69,7 +69,7 @@ __device__ __forceinline__ void params_body(int t, int nthreads, const double* _
         Mk[3] = -cp * ck; Mk[4] = -sk * cw_ - ck * sp * sw; Mk[5] = -sk * sw + cw_ * ck * sp;
         Mk[6] = 0.0;      Mk[7] = 0.0;                      Mk[8] = 0.0;
         if (ic) {  // BuildAwG.m:516-523, rows Xc Yc Zc w p k, 7 columns
-            double* g = G + (int64_t)t * 42;
+            double* g = G + (int64_t)t * G_BLK;
             // tan(phi), sec(phi) from the sincos above (equal to tan() / 1 / cos() to rounding)
             const double secp = 1.0 / cp, tp = sp * secp;
             const double rows[42] = {
@@ -146,23 +146,17 @@ __global__ __launch_bounds__(PARAMS_WG) void k_params(const double* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // Device layouts (observation-major so a thread / wave touches contiguous bytes):
-//   J   [o][JS], JS = 2*NJ + 2: Jacobian row x (NJ columns: 6 EOP | CW camera | 3 XYZ), row y, w
-//   WT  [o][18]: T = W Vinv at 3a+m, W = Je' P Jp (the back-substitution's only per-observation input)
-//   PT  [p][PS], PS = 12 + 6*CW: Vinv (00 01 02 11 12 22), vb = Vinv b, b, Wc[c][m], Tc = Wc Vinv
+//   J   [o][JS], JS = jac_stride(CW): Jacobian row x (NJ columns: 6 EOP | CW camera | 3 XYZ), row y, w
+//   WT  [o][T_ROW]: T = W Vinv at 3a+m, W = Je' P Jp (the back-substitution's only per-observation input)
+//   PT  [p][PS], PS = pt_stride(CW): Vinv (00 01 02 11 12 22), vb = Vinv b, b, Wc[c][m], Tc = Wc Vinv
 // ------------------------------------------------------------------------------------------------
 template <int NK>
-struct Lay {
-    static constexpr int CW = 5 + NK;
-    static constexpr int NJ = 9 + CW;
-    static constexpr int JS = 2 * NJ + 2;
-    static constexpr int PS = 12 + 6 * CW;
-};
+struct Lay : LayNK<NK> {};
 
-// The per-observation record of the back-substitution, WT[o] (OBS_REC = 12 doubles, 96 B): the raw
+// The per-observation record of the back-substitution, WT[o] (OBS_REC doubles, 96 B): the raw
 // tie-point Jacobian rows Jp (x: 0..2, y: 3..5) and the rotation columns of the EOP rows (x: 6..8, y:
 // 9..11).  The position columns of the EOP rows are -Jp (obs_model: d(UVW)/dXc = -d(UVW)/dX exactly),
 // masked by the EOP mask; so W = Je'PJp and T = W Vinv follow from the record and the point's Vinv.
-constexpr int OBS_REC = 12;
 __device__ __forceinline__ void obs_rec_rows(const double* __restrict__ r, unsigned eop_mask, double (&j0)[6],
                                              double (&j1)[6]) {
 #pragma unroll
@@ -432,12 +426,12 @@ __global__ __launch_bounds__(256) void k_lin_point(
         P[9] = b0; P[10] = b1; P[11] = b2;
 #pragma unroll
         for (int q = 0; q < CW; ++q) {
-            P[12 + 3 * q] = Wc[q][0];
-            P[13 + 3 * q] = Wc[q][1];
-            P[14 + 3 * q] = Wc[q][2];
-            P[12 + 3 * CW + 3 * q] = Wc[q][0] * I00 + Wc[q][1] * I01 + Wc[q][2] * I02;
-            P[13 + 3 * CW + 3 * q] = Wc[q][0] * I01 + Wc[q][1] * I11 + Wc[q][2] * I12;
-            P[14 + 3 * CW + 3 * q] = Wc[q][0] * I02 + Wc[q][1] * I12 + Wc[q][2] * I22;
+            P[PT_WC + 3 * q] = Wc[q][0];
+            P[PT_WC + 3 * q + 1] = Wc[q][1];
+            P[PT_WC + 3 * q + 2] = Wc[q][2];
+            P[pt_tc(CW) + 3 * q] = Wc[q][0] * I00 + Wc[q][1] * I01 + Wc[q][2] * I02;
+            P[pt_tc(CW) + 3 * q + 1] = Wc[q][0] * I01 + Wc[q][1] * I11 + Wc[q][2] * I12;
+            P[pt_tc(CW) + 3 * q + 2] = Wc[q][0] * I02 + Wc[q][1] * I12 + Wc[q][2] * I22;
         }
         vinv[t][0] = I00; vinv[t][1] = I01; vinv[t][2] = I02;
         vinv[t][3] = I11; vinv[t][4] = I12; vinv[t][5] = I22;
@@ -480,16 +474,16 @@ __constant__ int c_tri_b[21] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4, 0, 
 
 template <int NK>
 struct LR {
-    static constexpr int CW = 5 + NK;
+    static constexpr int CW = LayNK<NK>::CW;
     // row strides of the per-observation LDS rows: even (16-B aligned rows, ds_read_b128) and = 2 mod 4
     // doubles, so a row starts 4 x (odd) dwords apart from the next: 16 distinct bank quadruples over 16
     // rows (the (D) loops read the rows of random observations; a stride = 0 mod 4 doubles gives 8)
     static constexpr int ES = 14 + 2 * CW + ((14 + 2 * CW) % 4 == 0 ? 2 : 0);  // staging: Je | w | Jc (+ 2 for even nK)
-    static constexpr int US = 18;                   // U row (exactly)
+    static constexpr int US = T_ROW;                // U row (exactly)
     static_assert(ES % 4 == 2 && US % 4 == 2, "LDS row strides of 2 mod 4 doubles");
     static constexpr int PPS = 15 + 3 * CW;         // per-point: Vinv 6 | R 6 | rb 3 | Uc 3CW
-    static constexpr int NIMG = 27 + 6 * CW;        // image partial: 21 lower + 6 RHS + 6CW image-camera
-    static constexpr int NCAM = CW * (CW + 1) / 2 + CW;
+    static constexpr int NIMG = LayNK<NK>::NIMG;    // image partial: 21 lower + 6 RHS + 6CW image-camera
+    static constexpr int NCAM = LayNK<NK>::NCAM;
     // + ints: point of each observation, the chunk's plan (pair-key term offsets, terms, image-key
     // observation offsets, observations)
     static constexpr int CP = chunk_pts(NK), CT = chunk_terms(NK);
@@ -769,9 +763,9 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             const int q = qb + u;
             if (q < CW) {
                 const double w0_ = W1[u][0], w1_ = W1[u][1], w2_ = W1[u][2];
-                P[12 + 3 * CW + 3 * q] = w0_ * I00 + w1_ * I01 + w2_ * I02;
-                P[13 + 3 * CW + 3 * q] = w0_ * I01 + w1_ * I11 + w2_ * I12;
-                P[14 + 3 * CW + 3 * q] = w0_ * I02 + w1_ * I12 + w2_ * I22;
+                P[pt_tc(CW) + 3 * q] = w0_ * I00 + w1_ * I01 + w2_ * I02;
+                P[pt_tc(CW) + 3 * q + 1] = w0_ * I01 + w1_ * I11 + w2_ * I12;
+                P[pt_tc(CW) + 3 * q + 2] = w0_ * I02 + w1_ * I12 + w2_ * I22;
                 pp[15 + 3 * q] = w0_ * m00;
                 pp[16 + 3 * q] = w0_ * m10 + w1_ * m11;
                 pp[17 + 3 * q] = w0_ * m20 + w1_ * m21 + w2_ * m22;
@@ -810,7 +804,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
                 u[3 * a + 2] = v0 * r02 + v1 * r12 + v2 * r22;
             }
             if (urow) {
-                double2* ug = reinterpret_cast<double2*>(Ug + (int64_t)o * 18);
+                double2* ug = reinterpret_cast<double2*>(Ug + (int64_t)o * T_ROW);
 #pragma unroll
                 for (int m = 0; m < 9; ++m) ug[m] = double2{u[2 * m], u[2 * m + 1]};
             }
@@ -1006,9 +1000,9 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             }
             const int q0 = (GL == 8 && bA ? 4 * M : 0) + (bB ? 2 * M : 0) + (bC ? M : 0);
             // part 0: the 27 values at out[0 ..]; parts 1, 2: the 6 nq values of cameras columns
-            // (part - 1) HALF .. at out[27 + 6 (part - 1) HALF ..]
+            // (part - 1) HALF .. at out[IMG_PART_CAM + 6 (part - 1) HALF ..]
             const int nval = part == 0 ? 27 : 6 * min(HALF, CW - (part - 1) * HALF);
-            double* out = ipart + (int64_t)s_iks[K - ki0] * NIMG + (part == 0 ? 0 : 27 + 6 * (part - 1) * HALF);
+            double* out = ipart + (int64_t)s_iks[K - ki0] * NIMG + (part == 0 ? 0 : IMG_PART_CAM + 6 * (part - 1) * HALF);
 #pragma unroll
             for (int j = 0; j < M; ++j)
                 if (q0 + j < nval) out[q0 + j] = h1[j];
@@ -1042,7 +1036,7 @@ __global__ __launch_bounds__(LR_THREADS) void k_lin_reduce(
             }
             // (the key's row: pair-major slot, staged with the plan lists; 16-B aligned, as 6 double2 stores)
             double2* out = reinterpret_cast<double2*>(
-                ppart + (int64_t)(stage_terms ? s_pks[K - kp0] : A[plan.pk_slot + K]) * 36 + 6 * a0);
+                ppart + (int64_t)(stage_terms ? s_pks[K - kp0] : A[plan.pk_slot + K]) * PAIR_BLK + 6 * a0);
 #pragma unroll
             for (int q = 0; q < 6; ++q) out[q] = double2{-acc[2 * q], -acc[2 * q + 1]};
         }
@@ -1112,14 +1106,14 @@ __device__ __forceinline__ void red_pairs_body(int blk, const double* __restrict
     while (q + 4 <= q1) {
         double2 p[4][2];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { p[j][0] = pp[(int64_t)(q + j) * 18]; p[j][1] = pp[(int64_t)(q + j) * 18 + 3]; }
+        for (int j = 0; j < 4; ++j) { p[j][0] = pp[(int64_t)(q + j) * T_ROW]; p[j][1] = pp[(int64_t)(q + j) * T_ROW + 3]; }
 #pragma unroll
         for (int j = 0; j < 4; ++j) { add(s0, p[j][0]); add(s1, p[j][1]); }
         q += 4;
     }
     for (; q < q1; ++q) {
-        add(s0, pp[(int64_t)q * 18]);
-        add(s1, pp[(int64_t)q * 18 + 3]);
+        add(s0, pp[(int64_t)q * T_ROW]);
+        add(s1, pp[(int64_t)q * T_ROW + 3]);
     }
     // then the U-row terms (AccPlan::ck_tm chunks), in chunk order, TB in flight:
     // S(e1, e2)[r][c] -= U_a[r] . U_b[c], U rows of 6 x 3 (row r at 3 r: rows er, er + 1 of U_a and ec,
@@ -1138,8 +1132,8 @@ __device__ __forceinline__ void red_pairs_body(int blk, const double* __restrict
 #pragma unroll
         for (int u = 0; u < TB; ++u)
             if (u < nt) {
-                const double2* a = reinterpret_cast<const double2*>(Ug + (int64_t)oa[u] * 18 + 3 * er);
-                const double2* b = reinterpret_cast<const double2*>(Ug + (int64_t)ob[u] * 18 + 3 * ec);
+                const double2* a = reinterpret_cast<const double2*>(Ug + (int64_t)oa[u] * T_ROW + 3 * er);
+                const double2* b = reinterpret_cast<const double2*>(Ug + (int64_t)ob[u] * T_ROW + 3 * ec);
 #pragma unroll
                 for (int m = 0; m < 3; ++m) {
                     const double2 va = a[m], vb = b[m];
@@ -1209,7 +1203,6 @@ __device__ __forceinline__ void red_images_body(int e, const double* __restrict_
     }
 }
 
-constexpr int BW_SEG = 32;
 __device__ __forceinline__ void border_weights_body(int seg, const double* __restrict__ S, const double* __restrict__ G,
                                                     double* __restrict__ scal, double* __restrict__ part, int64_t ld,
                                                     int n_img, int n_loc, int ic, const int8_t* __restrict__ rown);
@@ -1217,7 +1210,6 @@ __device__ __forceinline__ void border_weights_body(int seg, const double* __res
 // camera block (lower) and camera RHS from the chunk partials of the camera, in two fixed-order
 // stages: k_red_cam_seg sums CAM_SEG contiguous segments of the camera's chunk list in parallel
 // (one workgroup each, 4 loads in flight per thread), k_red_cam adds the segment sums in order
-constexpr int CAM_SEG = 64;
 
 template <int NK>
 __device__ __forceinline__ void red_cam_seg_body(int sg, int q, int n_cam, const double* __restrict__ cpart,
@@ -1310,27 +1302,27 @@ __global__ __launch_bounds__(256) void k_red_cam(const double* __restrict__ cseg
 //                           M stays banded), w_m = 1 / sum_{i in loc} G_im^2 / S_ii (equilibrated)
 // and the exact bordered solution follows from the forward-solved right-hand sides
 //   r | A = G_l W_l^1/2 | B = G D   (D = the same equilibration over all images; B'x = 0 <=> G'x = 0)
-// in k_border_combine.  scal: [1] Cholesky failure flag, [2] sumabs, [8..14] W_l, [16..22] D^2.
+// in k_border_combine.  d_scal (fba_layout.h): SCAL_FAIL, SCAL_DSUM, W_l at SCAL_WL, D^2 at SCAL_D2.
 // ------------------------------------------------------------------------------------------------
 // k_border_weights: BW_SEG workgroups, each the 14 weight sums over a contiguous range of the 6 n_img
-// EOP rows -> part[seg][14]; the consumer (k_border_rhs) adds the segments in order (BW_SEG above)
+// EOP rows -> part[seg][BORDER_COLS]; the consumer (k_border_rhs) adds the segments in order
 
 // rown (subtree split, per row): the weight sums over all images (7..13) take only this rank's images'
 // rows -- a wholly-top image's diagonal is complete only after the ranks' sum (k_split_weights adds them)
 __device__ __forceinline__ void border_weights_body(int seg, const double* __restrict__ S, const double* __restrict__ G,
                                                     double* __restrict__ scal, double* __restrict__ part, int64_t ld,
                                                     int n_img, int n_loc, int ic, const int8_t* __restrict__ rown) {
-    __shared__ double red[4][14];
+    __shared__ double red[4][BORDER_COLS];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int64_t n = 6 * (int64_t)n_img;
     const int64_t i0 = n * seg / BW_SEG, i1 = n * (seg + 1) / BW_SEG;
-    double a[14];
+    double a[BORDER_COLS];
 #pragma unroll
-    for (int m = 0; m < 14; ++m) a[m] = 0.0;
+    for (int m = 0; m < BORDER_COLS; ++m) a[m] = 0.0;
     if (ic) {
         for (int64_t i = i0 + tid; i < i1; i += 256) {
             const double sii = S[i * ld + i];
-            const double* g = G + (i / 6) * 42 + (i % 6) * 7;
+            const double* g = G + (i / 6) * G_BLK + (i % 6) * G_ROW;
             const bool ok = sii > 0.0, loc = i < 6 * (int64_t)n_loc, all = !rown || rown[i] == 1;
             const double inv = ok ? 1.0 / sii : 0.0;
 #pragma unroll
@@ -1342,15 +1334,15 @@ __device__ __forceinline__ void border_weights_body(int seg, const double* __res
         }
     }
 #pragma unroll
-    for (int m = 0; m < 14; ++m) {
+    for (int m = 0; m < BORDER_COLS; ++m) {
         double v = a[m];
 #pragma unroll
         for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w, 64);
         if (lane == 0) red[wave][m] = v;
     }
     __syncthreads();
-    if (tid < 14) part[seg * 14 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    if (seg == 0 && tid == 0) scal[1] = 0.0;  // Cholesky failure flag
+    if (tid < BORDER_COLS) part[seg * BORDER_COLS + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    if (seg == 0 && tid == 0) scal[SCAL_FAIL] = 0.0;
 }
 
 __global__ __launch_bounds__(256) void k_border_weights(const double* __restrict__ S, const double* __restrict__ G,
@@ -1359,13 +1351,13 @@ __global__ __launch_bounds__(256) void k_border_weights(const double* __restrict
     border_weights_body(blockIdx.x, S, G, scal, part, ld, n_img, n_loc, ic, rown);
 }
 
-// the 14 weights (W_l: 0..6, D^2: 7..13) from the segment sums, into LDS w[14]; every thread calls it
+// the BORDER_COLS weights (W_l: 0..6, D^2: 7..13) from the segment sums, into LDS w[BORDER_COLS]; every thread calls it
 __device__ __forceinline__ void border_weights_lds(const double* __restrict__ part, double* w) {
     const int t = threadIdx.x;
-    if (t < 14) {
+    if (t < BORDER_COLS) {
         double x[BW_SEG];
 #pragma unroll
-        for (int g = 0; g < BW_SEG; ++g) x[g] = part[g * 14 + t];
+        for (int g = 0; g < BW_SEG; ++g) x[g] = part[g * BORDER_COLS + t];
         double v = 0.0;
 #pragma unroll
         for (int g = 0; g < BW_SEG; ++g) v += x[g];
@@ -1390,16 +1382,16 @@ __global__ __launch_bounds__(256) void k_border_rhs(double* __restrict__ S, cons
                                                     int64_t u_c, int n_img, int n_loc, int ic, int nbr,
                                                     unsigned* __restrict__ sync, int64_t n_sync, double* __restrict__ X,
                                                     const int8_t* __restrict__ rown, int rank) {
-    __shared__ double w[14];
+    __shared__ double w[BORDER_COLS];
     if (ic) border_weights_lds(part, w);
     if ((int)blockIdx.x < nbr) {
         const int64_t i = blockIdx.x;
-        const double* gi = G + (i / 6) * 42 + (i % 6) * 7;
+        const double* gi = G + (i / 6) * G_BLK + (i % 6) * G_ROW;
         double gw[7];
 #pragma unroll
         for (int m = 0; m < 7; ++m) gw[m] = gi[m] * w[m];
         for (int64_t j = threadIdx.x; j <= i; j += 256) {
-            const double* gj = G + (j / 6) * 42 + (j % 6) * 7;
+            const double* gj = G + (j / 6) * G_BLK + (j % 6) * G_ROW;
             double acc = 0.0;
 #pragma unroll
             for (int m = 0; m < 7; ++m) acc += gw[m] * gj[m];
@@ -1412,7 +1404,8 @@ __global__ __launch_bounds__(256) void k_border_rhs(double* __restrict__ S, cons
     const int64_t nthr = ((int64_t)gridDim.x - nbr) * blockDim.x;
     const int64_t i = ((int64_t)blockIdx.x - nbr) * blockDim.x + threadIdx.x;
     for (int64_t q = i; q < n_sync; q += nthr) sync[q] = 0u;
-    if (ic && blockIdx.x == nbr && threadIdx.x < 14) scal[8 + (threadIdx.x / 7) * 8 + threadIdx.x % 7] = w[threadIdx.x];
+    if (ic && blockIdx.x == nbr && threadIdx.x < BORDER_COLS)
+        scal[SCAL_WL + (threadIdx.x / G_ROW) * (SCAL_D2 - SCAL_WL) + threadIdx.x % G_ROW] = w[threadIdx.x];
     if (i >= n_pad) return;
     X[i] = __builtin_bit_cast(double, X_SENTINEL);  // k_bwd_flow's solution blocks: not yet published
     // (split: a wholly-top row's once-only entries on rank 0; another rank's rows are never read here)
@@ -1423,7 +1416,7 @@ __global__ __launch_bounds__(256) void k_border_rhs(double* __restrict__ S, cons
         S[n_pad * ld + i] = 0.0;
     }
     if (ic) {
-        const double* g = G + (i / 6) * 42 + (i % 6) * 7;
+        const double* g = G + (i / 6) * G_BLK + (i % 6) * G_ROW;
         for (int m = 0; m < 7; ++m) {
             S[(n_pad + 1 + m) * ld + i] = (i < 6 * (int64_t)n_loc) ? sqrt(w[m]) * g[m] : 0.0;  // A
             S[(n_pad + 8 + m) * ld + i] = (i < 6 * (int64_t)n_img && once) ? (rown ? g[m] : sqrt(w[7 + m]) * g[m]) : 0.0;  // B
@@ -1484,7 +1477,7 @@ __global__ __launch_bounds__(256) void k_backsub(const double* __restrict__ WT, 
         double d1 = P[7] + (P[1] * w0 + P[3] * w1 + P[4] * w2);
         double d2 = P[8] + (P[2] * w0 + P[4] * w1 + P[5] * w2);
         const double* dk = delta + 6 * (int64_t)n_img + (int64_t)lp_cam[p] * CW;
-        const double* Tc = P + 12 + 3 * CW;
+        const double* Tc = P + pt_tc(CW);
 #pragma unroll
         for (int k = 0; k < CW; ++k) {
             d0 += Tc[3 * k] * dk[k]; d1 += Tc[3 * k + 1] * dk[k]; d2 += Tc[3 * k + 2] * dk[k];
@@ -1502,14 +1495,14 @@ __global__ __launch_bounds__(256) void k_obs_T(const double* __restrict__ WT, co
     if (o >= n_obs) return;
     const int p = pt[o];
     if (p < 0) return;
-    obs_rec_T(WT + o * OBS_REC, PT + (int64_t)p * ps, eop_mask, px, py, T + o * 18);
+    obs_rec_T(WT + o * OBS_REC, PT + (int64_t)p * ps, eop_mask, px, py, T + o * T_ROW);
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // update: de-scale (main.m:460-482), xhat += delta, partial sumabs (fixed-order block sums)
 // ------------------------------------------------------------------------------------------------
-// (scal[1] < 0: a hand-off of the factorisation or backward solve timed out, fba_chol.hip -- delta is not
+// (scal[SCAL_FAIL] < 0: a hand-off of the factorisation or backward solve timed out, fba_chol.hip -- delta is not
 // a solution, xhat stays as it was and the host reports FBA_ERR_HIP)
 // a workgroup's 256 values summed in a fixed order (xor butterfly per wave, then the four wave sums in
 // order); every thread calls it, thread 0 returns the sum
@@ -1527,7 +1520,7 @@ __global__ __launch_bounds__(256) void k_update(double* __restrict__ xfull, doub
                                                 int cw, int cam_stride, const double* __restrict__ scal) {
     __shared__ double red[4];
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool apply = !(scal[1] < 0.0);
+    const bool apply = !(scal[SCAL_FAIL] < 0.0);
     double a = 0.0;
     if (i < u_full) {
         double d = delta[i];
@@ -1548,7 +1541,7 @@ __global__ __launch_bounds__(256) void k_update(double* __restrict__ xfull, doub
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// deltasum into scal[2]; scal[0..3] also to the host-mapped scratch `host` (read after the stream sync)
+// deltasum into scal[SCAL_DSUM]; the slots below SCAL_MIRROR also to the host-mapped scratch `host` (read after the stream sync)
 __global__ void k_sum_parts(const double* __restrict__ part, int n, double* __restrict__ scal, double* __restrict__ host) {
     __shared__ double red[4];
     double a = 0.0;
@@ -1564,18 +1557,18 @@ __global__ void k_sum_parts(const double* __restrict__ part, int n, double* __re
     }
     const double sum = block_sum256(a, red);
     if (threadIdx.x == 0) {
-        scal[2] = sum;
+        scal[SCAL_DSUM] = sum;
         if (host) {
-            host[0] = scal[0];
-            host[1] = scal[1];
-            host[2] = sum;
-            host[3] = scal[3];
+            host[SCAL_SPARE0] = scal[SCAL_SPARE0];
+            host[HPIN_FAIL] = scal[SCAL_FAIL];
+            host[HPIN_DSUM] = sum;
+            host[SCAL_SPARE3] = scal[SCAL_SPARE3];
             // the solve's sequence number last, behind the values (the host polls it instead of waiting
             // for the stream: this kernel ends every solve)
             __threadfence_system();
-            const double seq = scal[5] + 1.0;
-            scal[5] = seq;
-            host[4] = seq;
+            const double seq = scal[SCAL_SEQ] + 1.0;
+            scal[SCAL_SEQ] = seq;
+            host[HPIN_SEQ] = seq;
         }
     }
 }
@@ -1786,7 +1779,7 @@ __global__ __launch_bounds__(256) void k_residuals(const double* __restrict__ J,
         const double xb = xy[2 * o] - kp[0], yb = xy[2 * o + 1] - kp[1];
         const double theta = atan2(yb, xb), phi = atan2(vv[1], vv[0]);
         const double vd = sqrt(vv[0] * vv[0] + vv[1] * vv[1]);
-        double* rr = rsd + 5 * o;
+        double* rr = rsd + RSD_ROW * o;
         rr[0] = sqrt(xb * xb + yb * yb);
         rr[1] = vv[0];
         rr[2] = vv[1];
@@ -1821,7 +1814,7 @@ __global__ __launch_bounds__(256) void k_build_rsd(const double* __restrict__ xy
     const double xb = xy[2 * o] - xpyp[2 * cam[o]], yb = xy[2 * o + 1] - xpyp[2 * cam[o] + 1];
     const double theta = atan2(yb, xb), phi = atan2(vy, vx);
     const double vd = sqrt(vx * vx + vy * vy);
-    double* r = rsd + 5 * i;
+    double* r = rsd + RSD_ROW * i;
     r[0] = sqrt(xb * xb + yb * yb);
     r[1] = vx;
     r[2] = vy;
@@ -2002,7 +1995,7 @@ int launch_accumulate(Ctx& c, bool zeroed) {
     // damping rides on the WH = true instantiations (s = 1 without weights or a loss): the undamped,
     // unweighted default launches the WH = false kernels as before
     const bool lr_wh = c.whiten_on() || c.damp_on();
-    const BorderW bw{c.d_G, c.d_scal, c.d_bscr, c.n_loc, c.set.inner_constraints};
+    const BorderW bw{c.d_G, c.d_scal, c.d_bscr + BSC_WSEG, c.n_loc, c.set.inner_constraints};
     FBA_NK_DISPATCH(L.nk, ACC);
 #undef ACC
 #undef LR_ARGS
@@ -2030,12 +2023,12 @@ int launch_border(Ctx& c) {
     const int ic = c.set.inner_constraints;
     const int8_t* rown = c.sched.split ? c.d_rown : nullptr;
     if (!border_weights_in_accumulate(c)) {
-        k_border_weights<<<BW_SEG, 256, 0, c.stream>>>(c.d_S, c.d_G, c.d_scal, c.d_bscr, L.ld, L.n_img, c.n_loc, ic, rown);
+        k_border_weights<<<BW_SEG, 256, 0, c.stream>>>(c.d_S, c.d_G, c.d_scal, c.d_bscr + BSC_WSEG, L.ld, L.n_img, c.n_loc, ic, rown);
         FBA_HIP(hipGetLastError());
     }
     const int nbr = (ic && c.n_loc > 0) ? 6 * c.n_loc : 0;
     k_border_rhs<<<(unsigned)(nbr + (L.n_pad + 255) / 256), 256, 0, c.stream>>>(
-        c.d_S, c.d_G, c.d_scal, c.d_bscr, c.d_active, L.ld, L.n_pad, L.u_c, L.n_img, c.n_loc, ic, nbr, c.d_flags,
+        c.d_S, c.d_G, c.d_scal, c.d_bscr + BSC_WSEG, c.d_active, L.ld, L.n_pad, L.u_c, L.n_img, c.n_loc, ic, nbr, c.d_flags,
         c.n_sync, c.d_X, rown, c.opt.rank);
     FBA_HIP(hipGetLastError());
     return FBA_OK;
@@ -2193,9 +2186,9 @@ __global__ void k_pack(double* __restrict__ S, int64_t ld, double* __restrict__ 
 //   [the accumulated diagonal of the top rows carrying image unknowns, packed before the subtree flow]
 //   [Gram partials (16 x 16) of every non-top block column: this rank's own, zeros for the others']
 //   [this rank's 7 inner-constraint weight sums over its subtree rows (k_border_weights' segments)]
-//   [1: this rank's flow A aborted (a hand-off timed out, scal[1] < 0): its top-block contributions are
+//   [1: this rank's flow A aborted (a hand-off timed out, scal[SCAL_FAIL] < 0): its top-block contributions are
 //    incomplete; after the sum every rank sees it, raises the abort ahead of flow B and fails the step]
-//   [1: this rank's flow A met a non-positive pivot (scal[1] = row + 1 > 0): after the sum every rank reports
+//   [1: this rank's flow A met a non-positive pivot (scal[SCAL_FAIL] = row + 1 > 0): after the sum every rank reports
 //    it, so the ranks agree that the step failed]
 // dir 0: S (+ gblk, weight segments) -> buffer; dir 1: buffer -> S top blocks, gblk.  (The diagonal part
 // is written by k_pack_topdiag ahead of the subtree flow.)
@@ -2224,29 +2217,29 @@ __global__ __launch_bounds__(256) void k_pack_split(double* __restrict__ S, int6
         for (int k = 0; k < nb; ++k) {
             if (bown[k] == 2) continue;
             for (int e = threadIdx.x; e < 256; e += 256) {
-                if (dir == 0) red[red_gblk + 256 * (int64_t)g + e] = bown[k] == 1 ? gblk[256 * (int64_t)k + e] : 0.0;
-                else gblk[256 * (int64_t)k + e] = red[red_gblk + 256 * (int64_t)g + e];
+                if (dir == 0) red[red_gblk + GRAM_BLK * (int64_t)g + e] = bown[k] == 1 ? gblk[GRAM_BLK * (int64_t)k + e] : 0.0;
+                else gblk[GRAM_BLK * (int64_t)k + e] = red[red_gblk + GRAM_BLK * (int64_t)g + e];
             }
             ++g;
         }
         if (dir == 0 && threadIdx.x < 7) {
             double v = 0.0;
-            for (int sg = 0; sg < 32; ++sg) v += wseg[sg * 14 + 7 + threadIdx.x];  // (BW_SEG segments)
+            for (int sg = 0; sg < BW_SEG; ++sg) v += wseg[sg * BORDER_COLS + G_ROW + threadIdx.x];
             red[red_w + threadIdx.x] = v;
         }
         if (threadIdx.x == 7) {
-            // (flow A has finished: k_pack_split follows it on the stream, so scal[1] is final here)
-            const double f = scal[1];
+            // (flow A has finished: k_pack_split follows it on the stream, so scal[SCAL_FAIL] is final here)
+            const double f = scal[SCAL_FAIL];
             if (dir == 0) {
                 red[red_w + 7] = f < 0.0 ? 1.0 : 0.0;  // a hand-off timed out
                 red[red_w + 8] = f > 0.0 ? f : 0.0;    // a non-positive pivot at row f - 1 of this rank's subtree
             } else if (red[red_w + 7] != 0.0) {
-                scal[1] = -1.0;  // some rank's flow A aborted: skip flow B, k_update
+                scal[SCAL_FAIL] = -1.0;  // some rank's flow A aborted: skip flow B, k_update
             } else if (red[red_w + 8] != 0.0 && f == 0.0) {
                 // some rank's flow A hit a non-positive pivot: every rank reports it (FBA_ERR_NOT_SPD), as the
                 // failing rank does, instead of solving on top blocks that hold its bad Schur updates
                 // (the row is the failing rank's, or the sum of the rows when several ranks failed)
-                scal[1] = red[red_w + 8];
+                scal[SCAL_FAIL] = red[red_w + 8];
             }
         }
     }
@@ -2272,7 +2265,7 @@ __global__ __launch_bounds__(256) void k_split_weights(const double* __restrict_
         const int64_t i = rows[q];
         const double sii = red[red_diag + q];
         const double inv = sii > 0.0 ? 1.0 / sii : 0.0;
-        const double* g = G + (i / 6) * 42 + (i % 6) * 7;
+        const double* g = G + (i / 6) * G_BLK + (i % 6) * G_ROW;
 #pragma unroll
         for (int m = 0; m < 7; ++m) a[m] += g[m] * g[m] * inv;
     }
@@ -2284,7 +2277,7 @@ __global__ __launch_bounds__(256) void k_split_weights(const double* __restrict_
         for (int t = 0; t < 256; ++t) v += part[t][threadIdx.x];
         const double w = v > 0.0 ? 1.0 / v : 1.0;
         bsc[threadIdx.x] = sqrt(w);
-        scal[16 + threadIdx.x] = w;
+        scal[SCAL_D2 + threadIdx.x] = w;
     }
 }
 
@@ -2299,11 +2292,11 @@ int launch_pack_split(Ctx& c, int dir) {
     }
     k_pack_split<<<(unsigned)(s.n_top_blocks + 1), 256, 0, c.stream>>>(
         c.d_S, c.L.ld, c.d_red, c.d_sched + s.top_blocks, s.n_top_blocks, c.L.n_pad, c.L.nrhs, c.d_gblk, c.d_bown,
-        (int)(c.L.n_pad / 128), c.red_gblk, c.red_w, c.d_bscr, c.d_scal, dir);
+        (int)(c.L.n_pad / 128), c.red_gblk, c.red_w, c.d_bscr + BSC_WSEG, c.d_scal, dir);
     FBA_HIP(hipGetLastError());
     if (dir == 1 && c.set.inner_constraints) {
         k_split_weights<<<1, 256, 0, c.stream>>>(c.d_red, c.red_diag, c.red_w, c.d_topdiag, c.n_topdiag, c.d_G,
-                                                 c.d_bscr + BSC_OFF, c.d_scal);
+                                                 c.d_bscr + BSC_SCALE, c.d_scal);
         FBA_HIP(hipGetLastError());
     }
     return FBA_OK;

@@ -243,7 +243,7 @@ void plan_layout(Ctx& c, Work& w) {
     // camera-side order of the images: nested dissection with padding slots (fba_order.cpp)
     c.img_ord = camera_order(p);
     compute_layout(p, s, L, (int)c.img_ord.size());
-    c.cam_tab_stride = CAM_TAB_HDR + 3 * L.nk;  // header | K_j | rmax^(2j) | rmax^-(2j)
+    c.cam_tab_stride = cam_tab_row(L.cw);  // header | K_j | rmax^(2j) | rmax^-(2j)
     c.img_new.assign(L.n_img_ref, 0);
     for (int e = 0; e < L.n_img; ++e)
         if (c.img_ord[e] >= 0) c.img_new[c.img_ord[e]] = e;

@@ -229,8 +229,8 @@ __global__ __launch_bounds__(256) void k_rel_pts(RelMat M, const double* __restr
     RelRows R;
     R.ni = m; R.nc = 1; R.cw = cw; R.n = 6 * m + cw;
     R.gimg = img + o0; R.gcam = lp_cam + p;
-    R.Ti = WT + (int64_t)o0 * 18; R.ti_stride = 18;
-    R.Tc = P + 12 + 3 * cw; R.tc_stride = 0;
+    R.Ti = WT + (int64_t)o0 * T_ROW; R.ti_stride = T_ROW;
+    R.Tc = P + pt_tc(cw); R.tc_stride = 0;
     R.cam_base = 6 * (int64_t)n_img;
     rel_point<true>(R, M, P, X, cpp, wt, rows);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nj = 9 + cw;
@@ -254,12 +254,12 @@ __global__ __launch_bounds__(256) void k_rel_gen(RelMat M, const double* __restr
     RelRows R;
     R.ni = ni; R.nc = nc; R.cw = cw; R.n = 6 * ni + cw * nc;
     R.gimg = A + g.gi_img + i0; R.gcam = A + g.gc_cam + c0;
-    R.Ti = gug + (int64_t)i0 * 36 + 18; R.ti_stride = 36;
-    R.Tc = gcu + (int64_t)c0 * 6 * cw + 3 * cw; R.tc_stride = 6 * cw;
+    R.Ti = gug + (int64_t)i0 * GUG + GUG_T; R.ti_stride = GUG;
+    R.Tc = gcu + (int64_t)c0 * 6 * cw + 3 * cw; R.tc_stride = gpc_tab(cw);  // (row c0 of gpc_tab(cw), its Tc half)
     R.cam_base = 6 * (int64_t)n_img;
     // this point's X: [6 ni rows of its gimgs | cw nc rows of its gpcs], at the offset of all earlier points'
     double* X = Xg + 3 * (6 * (int64_t)i0 + (int64_t)cw * c0);
-    rel_point<false>(R, M, gpt + pq * 18, X, cpp, wt, nullptr);
+    rel_point<false>(R, M, gpt + pq * GPT, X, cpp, wt, nullptr);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nj = 9 + cw;
     for (int gi = wave; gi < ni; gi += 4) {
         const int xc = A[g.gi_gc + i0 + gi] - c0;  // the gpc of the image's camera
@@ -311,14 +311,13 @@ int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d
     const Layout& L = c.L;
     const GenPlan& g = c.gen;
     int rc;
-    auto alloc = [&](double** p, size_t n) -> int { return ws_get(c, si.next_slot++, sizeof(double) * std::max<size_t>(n, 1), (void**)p); };
     const RelMat M{c.d_S, L.ld, si.d_Z, si.d_Wz, si.nz, L.n_pad};
     FBA_HIP(hipMemsetAsync(d_red, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
     FBA_HIP(hipMemsetAsync(d_wst, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
     if (c.n_obs == 0) return FBA_OK;
     if ((rc = launch_residuals(c))) return rc;  // v of the last linearisation (d_J) and correction, as fba_residuals
     if (c.n_lp > 0) {
-        if (!si.d_T && ((rc = alloc(&si.d_T, (size_t)18 * std::max<int64_t>(c.n_obs_tie, 1))) || (rc = launch_obs_T(c, si.d_T))))
+        if (!si.d_T && ((rc = ws_get(c, WS_OBS_T, (size_t)T_ROW * std::max<int64_t>(c.n_obs_tie, 1), &si.d_T)) || (rc = launch_obs_T(c, si.d_T))))
             return rc;
         k_rel_pts<<<(unsigned)c.n_lp, 256, 0, c.stream>>>(M, c.d_J, c.ncomp, si.d_T, c.d_pt_tab, c.pt_comp, c.d_lp_start,
                                                          c.d_lp_cam, c.d_img, L.n_img, L.cw, d_q);
@@ -329,7 +328,7 @@ int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d
                                                                                   c.n_obs_tie, c.n_obs, L.n_img, L.cw, d_q);
     if (g.n_gp > 0) {
         double* d_Xg = nullptr;
-        if ((rc = alloc(&d_Xg, (size_t)3 * (6 * (size_t)g.n_gi + (size_t)L.cw * g.n_gc)))) return rc;
+        if ((rc = ws_get(c, WS_REL_XG, (size_t)3 * (6 * (size_t)g.n_gi + (size_t)L.cw * g.n_gc), &d_Xg))) return rc;
         k_rel_gen<<<(unsigned)g.n_gp, 256, 0, c.stream>>>(M, c.d_J, c.ncomp, c.d_acc, g, c.d_gpt, c.d_gcu, c.d_gug, L.n_img,
                                                          L.cw, d_Xg, d_q);
     }

@@ -477,6 +477,10 @@ int fba_set_spin_bound(fba_ctx* ctx, int64_t spins);
  * [[A'A - I, A'B], [B'A, B'B]] [z; k] = -[A'y; B'y]. */
 int fba_test_border_solve(int32_t device, const double* gram /*[225]*/, double* coef /*[14]*/);
 
+/* Test hook (no reference counterpart): the number of device and pinned allocations the library holds in
+ * this process right now, over all contexts.  fba_destroy, and a failed fba_create, leave it where it was. */
+int fba_test_live_allocations(int64_t* n);
+
 #ifdef __cplusplus
 }
 #endif
