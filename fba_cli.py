@@ -8,6 +8,9 @@
     ... main <folder> ... --intersect          the tie points' starting values by forward intersection of their image
                                                rays instead of the .cnt coordinates; also writes the .fwd table
                                                (report.write_fwd)
+    ... main <folder> ... --resect[=control|all]  the images' starting values by space resection from their control
+                                               points (all: and the tie points at their .cnt coordinates) instead of
+                                               the .ext values; also writes the .rsc table (report.write_rsc)
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
     ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
                                                of sigma (default: the 95 %-efficiency constants, huber 1.345,

@@ -117,6 +117,23 @@ def parse_intersect(args):
     return [a for a in args if a != "--intersect"], "--intersect" in args
 
 
+def parse_resect(args):
+    """--resect, --resect=control or --resect=all anywhere in args -> (args without it, False / "control" / "all"):
+    the images' starting values by space resection (`main` only; writes the .rsc table).  ValueError for another
+    class."""
+    rest, resect = [], False
+    for a in args:
+        if a == "--resect":
+            resect = "control"
+        elif a.startswith("--resect="):
+            resect = a.split("=", 1)[1].lower()
+            if resect not in ("control", "all"):
+                raise ValueError("--resect: control or all")
+        else:
+            rest.append(a)
+    return rest, resect
+
+
 def parse_robust(args):
     """--robust huber[:k] | cauchy[:k] (also --robust=...) anywhere in args -> (args without it, loss or None,
     k or None).  ValueError for a missing or unknown loss, or a k that is not a positive number."""
@@ -148,12 +165,13 @@ def parse_robust(args):
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
     anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors', --lm parse_lm's)"""
+    args = parse_resect(args)[0]
     args = parse_intersect(parse_ellipsoids(parse_lm(parse_priors(parse_robust(args)[0])[0])[0])[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--resect[=control|all]] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
          "batch <folder>... [--robust LOSS[:k]] [--priors] [--lm[=lambda0]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
          "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
          "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
@@ -162,7 +180,9 @@ USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] 
          "      the Gauss-Newton loop: for coarse starting values; writes the .lm table\n  --ellipsoids  (main) every tie "
          "point's full 3 x 3 covariance and 1-sigma error ellipsoid; writes the .ell table\n  --intersect  (main) the tie "
          "points' starting values by forward intersection of their image rays instead of the .cnt\n      coordinates; "
-         "writes the .fwd table")
+         "writes the .fwd table\n  --resect[=control|all]  (main) the images' starting values by space resection from their control "
+         "points (all: and\n      the tie points at their .cnt coordinates) instead of the .ext values; writes the .rsc "
+         "table")
 
 
 def cli(argv=None):
@@ -175,6 +195,7 @@ def cli(argv=None):
         argv, robust, robust_k = parse_robust(argv)
         argv, ellipsoids = parse_ellipsoids(argv)
         argv, intersect = parse_intersect(argv)
+        argv, resect = parse_resect(argv)
     except ValueError as e:
         print(f"Error: {e}")
         print(USAGE)
@@ -184,7 +205,7 @@ def cli(argv=None):
         folder, plot, reliability = parse_main(argv[1:])
         return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors),
                     **_lm_kw(lm), **({"ellipsoids": True} if ellipsoids else {}),
-                    **({"intersect": True} if intersect else {}))
+                    **({"intersect": True} if intersect else {}), **({"resect": resect} if resect else {}))
     if len(argv) >= 2 and argv[0] == "batch":
         done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors), **({"lm": lm} if lm else {}))
         return 1 if any(e for _, e in done) else 0

@@ -102,6 +102,12 @@ class Adjustment:
     isect_xyz: np.ndarray = None      # (n_tie, 3)
     isect_quality: np.ndarray = None  # (n_tie, 4)
     isect_status: np.ndarray = None   # (n_tie)
+    # space resection of the starting values (resect=...), EXT order: the resected Xc Yc Zc omega phi kappa, per image
+    # [points used, lambda_1 / lambda_11, RMS px linear, RMS px refined, share in front], FBA_RESECT_*
+    # (capi.RESECT_STATUS)
+    resect_eop: np.ndarray = None      # (n_img, 6)
+    resect_quality: np.ndarray = None  # (n_img, 5)
+    resect_status: np.ndarray = None   # (n_img)
 
 
 def _priors_of(data, priors):
@@ -128,7 +134,7 @@ def prior_statistics(sigma02, cx_diag, index, sigma, v):
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
            reliability=False, priors=None, method="gn", lm_options=None, point_precision=False,
-           intersect=False) -> Adjustment:
+           intersect=False, resect=False) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -161,7 +167,17 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     "lm", every tie point is intersected from its image rays at the starting exterior and interior orientation
     (fba_intersect with write_xhat: linear line intersection, then point-only Gauss-Newton) and replaces its .cnt
     starting value; a point with fewer than two usable rays or too flat an intersection keeps it.
-    Adjustment.isect_xyz, isect_quality and isect_status carry the result."""
+    Adjustment.isect_xyz, isect_quality and isect_status carry the result.
+
+    resect (no reference counterpart: Buildxhat.m:22-63 copies the .ext rows): True or "control" -- before the
+    intersection and the loop, "gn" or "lm", every image is resected from its control points and their measured rays
+    (fba_resect with write_xhat: a linear ray-based solution, then Gauss-Newton on the image's six unknowns) and
+    replaces its .ext starting values; "all" also uses the tie observations at their .cnt coordinates.  An image
+    with fewer than six usable points or points too close to a plane keeps its .ext values.  With intersect=True
+    the chain resection, intersection, adjustment starts a block from control points and measurements alone.
+    Adjustment.resect_eop, resect_quality and resect_status carry the result."""
+    if resect not in (False, None, True, "control", "all"):
+        raise ValueError(f"adjust: unknown resect {resect!r} (True, \"control\" or \"all\")")
     if method not in ("gn", "lm"):
         raise ValueError(f"adjust: unknown method {method!r} (\"gn\" or \"lm\")")
     t0 = time.perf_counter()
@@ -172,9 +188,12 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
             ctx.set_weights(weights)
         lmh = None
         ikw = {}
+        if resect:
+            re, rq, rst, _ = ctx.resect(use="all" if resect == "all" else "control", write_xhat=True)
+            ikw = dict(resect_eop=re, resect_quality=rq, resect_status=rst)
         if intersect:
             ix, iq, ist, _ = ctx.intersect(write_xhat=True)
-            ikw = dict(isect_xyz=ix, isect_quality=iq, isect_status=ist)
+            ikw.update(isect_xyz=ix, isect_quality=iq, isect_status=ist)
         if method == "lm":
             nt, npol, lmh = ctx.adjust_lm(lm_options)
             it, hist = nt + npol, lmh[:, 2].copy()
@@ -235,11 +254,13 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_ell(os.path.join(folder, name + ".ell"), data, res)
     if getattr(res, "isect_status", None) is not None:
         report.write_fwd(os.path.join(folder, name + ".fwd"), data, res)
+    if getattr(res, "resect_status", None) is not None:
+        report.write_rsc(os.path.join(folder, name + ".rsc"), data, res)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False) -> int:
+         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False, resect=False) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
@@ -249,7 +270,8 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
     in place of the Gauss-Newton loop; the .lm table (report.write_lm) is written too.  ellipsoids=True:
     adjust()'s point_precision; the .ell table (report.write_ell) is written too.  intersect=True: adjust()'s
     intersect -- the tie points' starting values from their image rays instead of the .cnt file; the .fwd table
-    (report.write_fwd) is written too."""
+    (report.write_fwd) is written too.  resect=True / "control" / "all": adjust()'s resect -- the images' starting
+    values by space resection instead of the .ext file; the .rsc table (report.write_rsc) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
@@ -258,6 +280,7 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
                      **({"priors": True} if priors else {}),
                      **({"point_precision": True} if ellipsoids else {}),
                      **({"intersect": True} if intersect else {}),
+                     **({"resect": resect} if resect else {}),
                      **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:

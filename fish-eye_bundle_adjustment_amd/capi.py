@@ -21,6 +21,8 @@ LOSS_K = {"huber": 1.345, "cauchy": 2.385}
 NK_MAX = 8
 RAY_STATUS = ("ok", "domain")                    # FBA_RAY_*
 ISECT_STATUS = ("ok", "few", "weak", "refine")   # FBA_ISECT_*
+RESECT_STATUS = ("ok", "few", "weak", "refine")  # FBA_RESECT_*
+RESECT_USE = ("control", "all")                  # FBA_RESECT_USE_*
 
 # every symbol include/fba.h declares
 EXPORTS = (
@@ -34,6 +36,7 @@ EXPORTS = (
     "fba_set_damping", "fba_cost", "fba_adjust_lm",
     "fba_postfit_outputs",
     "fba_unproject_host", "fba_image_rays", "fba_intersect",
+    "fba_resect", "fba_resect_host",
 )
 # ... but for the host-only helpers whose names carry a digit (tests/test_damping_host.py reads the header's
 # declarations with a letters-only pattern and compares them with EXPORTS)
@@ -90,6 +93,20 @@ class IntersectOptions(C.Structure):
     def __init__(self, refine_iters=10, write_xhat=False, min_ratio=0.5 * (1.0 - np.cos(np.pi / 180.0)),
                  refine_tol=1e-10):
         super().__init__(int(refine_iters), int(bool(write_xhat)), float(min_ratio), float(refine_tol))
+
+
+class ResectOptions(C.Structure):
+    """fba_resect_options; the defaults are the library's (a NULL pointer).  use: "control", "all" or the
+    FBA_RESECT_USE_* number"""
+    _fields_ = [("use", C.c_int32), ("refine_iters", C.c_int32), ("write_xhat", C.c_int32), ("reserved", C.c_int32),
+                ("min_ratio", C.c_double), ("refine_tol", C.c_double)]
+
+    def __init__(self, use="control", refine_iters=10, write_xhat=False, min_ratio=1e-6, refine_tol=1e-10):
+        if isinstance(use, str):
+            if use.lower() not in RESECT_USE:
+                raise ValueError(f"resect: unknown use {use!r} (one of {', '.join(RESECT_USE)})")
+            use = RESECT_USE.index(use.lower())
+        super().__init__(int(use), int(refine_iters), int(bool(write_xhat)), 0, float(min_ratio), float(refine_tol))
 
 
 def pack_priors(priors):
@@ -161,6 +178,8 @@ def _load():
         "fba_unproject_host": ([I, I, C.c_int64, P, P, P, P], C.c_int),
         "fba_image_rays": ([P, P, P], C.c_int),
         "fba_intersect": ([P, P, P, P, P, P], C.c_int),
+        "fba_resect": ([P, P, P, P, P, P], C.c_int),
+        "fba_resect_host": ([I, C.c_int64, P, P, P, D, D, D, D, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -484,6 +503,21 @@ class Context:
         check(lib.fba_intersect(self.h, C.byref(op), ptr(xyz), ptr(q), ptr(st), C.byref(bad)))
         return xyz[:nt], q[:nt], st[:nt], bad.value
 
+    def resect(self, use="control", refine_iters=10, write_xhat=False, min_ratio=1e-6, refine_tol=1e-10):
+        """fba_resect: (eop, quality, status, n_not_ok) -- every image resected from object points and its measured
+        image rays at the device xhat, EXT order: eop (n_img, 6) Xc Yc Zc omega phi kappa; quality (n_img, 5): points
+        used, lambda_1 / lambda_11 of the linear solution's Gram matrix, RMS reprojection residual (px) of the linear
+        and of the refined solution, the share of the used points in front (d . M (X - C) > 0); status (n_img)
+        FBA_RESECT_* (capi.RESECT_STATUS); the number of images not OK.  use: "control" (control observations only)
+        or "all" (also the tie observations at the device xhat's tie coordinates).  write_xhat: the OK and REFINE
+        images replace their six entries of the device xhat.  One GPU only (world == 1)."""
+        ni = self.packed.n_img
+        op = ResectOptions(use, refine_iters, write_xhat, min_ratio, refine_tol)
+        eop, q, st = np.zeros((max(ni, 1), 6)), np.zeros((max(ni, 1), 5)), np.zeros(max(ni, 1), dtype=np.int32)
+        bad = C.c_int64()
+        check(lib.fba_resect(self.h, C.byref(op), ptr(eop), ptr(q), ptr(st), C.byref(bad)))
+        return eop[:ni], q[:ni], st[:ni], bad.value
+
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""
         check(lib.fba_set_spin_bound(self.h, int(spins)))
@@ -532,6 +566,29 @@ def unproject_host(typ, xy, camtab):
     out, st = np.zeros((max(len(xy), 1), 5)), np.zeros(max(len(xy), 1), dtype=np.int32)
     check(lib.fba_unproject_host(t, ct.size - 6, len(xy), ptr(xy) if len(xy) else None, ptr(ct), ptr(out), ptr(st)))
     return out[: len(xy)], st[: len(xy)]
+
+
+def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, refine_iters=10, min_ratio=1e-6,
+                refine_tol=1e-10):
+    """fba_resect_host: the device's per-image resection (csrc/fba_resect.h) run on the CPU for one image, no GPU
+    needed.  typ: a name of TYPES or the FBA_TYPE_* number; xyz (n, 3) object points; ray (n, 5) unproject_host's
+    rows of their measurements; ray_status (n) FBA_RAY_* or None; c, ydir of the camera -> (eop (6), quality (5),
+    status): Context.resect's row of one image, eop zeros for FEW and WEAK."""
+    t = TYPES.index(typ) if isinstance(typ, str) else int(typ)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    ray = np.ascontiguousarray(ray, dtype=np.float64).reshape(-1, 5)
+    if len(xyz) != len(ray):
+        raise ValueError("resect_host: one ray per object point expected")
+    rs = None if ray_status is None else np.ascontiguousarray(ray_status, dtype=np.int32).reshape(-1)
+    if rs is not None and len(rs) != len(xyz):
+        raise ValueError("resect_host: one ray status per object point expected")
+    op = ResectOptions("control", refine_iters, False, min_ratio, refine_tol)
+    eop, q, st = np.zeros(6), np.zeros(5), C.c_int32()
+    n = len(xyz)
+    check(lib.fba_resect_host(t, n, ptr(xyz) if n else None, ptr(ray) if n else None, ptr(rs) if (rs is not None and n) else None,
+                              float(c), float(ydir), float(std_x), float(std_y), C.byref(op), ptr(eop), ptr(q),
+                              C.byref(st)))
+    return eop, q, st.value
 
 
 def tie_blocks(cx_tie):

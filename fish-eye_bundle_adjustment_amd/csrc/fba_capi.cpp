@@ -23,6 +23,7 @@
 #include "fba_internal.h"
 #include "fba_eig3.h"
 #include "fba_ray.h"
+#include "fba_resect.h"
 
 namespace fba {
 
@@ -1326,6 +1327,123 @@ int fba_intersect(fba_ctx* ctx, const fba_intersect_options* o, double* xyz, dou
         std::fill(c->last_ms, c->last_ms + 8, 0.0);
         c->last_ms[7] = ms;
     }
+    return FBA_OK;
+}
+
+// ---- space resection (no reference counterpart; kernels in fba_resect.hip, per-image routines in fba_resect.h) ----
+namespace fba {
+static const fba_resect_options kResectDefaults{FBA_RESECT_USE_CONTROL, 10, 0, 0, 1e-6, 1e-10};
+static int check_resect_options(const char* who, const fba_resect_options& op) {
+    if ((op.use != FBA_RESECT_USE_CONTROL && op.use != FBA_RESECT_USE_ALL) || op.refine_iters < 0 ||
+        !std::isfinite(op.min_ratio) || op.min_ratio < 0.0 || !std::isfinite(op.refine_tol) || op.refine_tol < 0.0) {
+        set_error(std::string(who) + ": use CONTROL or ALL, refine_iters >= 0, min_ratio and refine_tol finite and >= 0");
+        return FBA_ERR_ARG;
+    }
+    return FBA_OK;
+}
+// the image list on first use: d_img downloaded once, sorted on the host (build_image_list), kept by the context
+static int image_list_once(Ctx* c) {
+    if (c->have_img_list) return FBA_OK;
+    std::vector<int32_t> img((size_t)c->n_obs), start, list;
+    if (c->n_obs > 0) FBA_HIP(hipMemcpy(img.data(), c->d_img, sizeof(int32_t) * img.size(), hipMemcpyDeviceToHost));
+    build_image_list(img, c->L.n_img, start, list);
+    if ((int64_t)list.size() != c->n_obs) { set_error("fba_resect: an observation's image slot is out of range"); return FBA_ERR_ARG; }
+    int rc;
+    if ((rc = upload(*c, &c->d_il_start, start)) || (rc = upload(*c, &c->d_il_obs, list)) ||
+        (rc = upload(*c, &c->d_il_ext, c->img_ord)))
+        return rc;
+    c->have_img_list = true;
+    return FBA_OK;
+}
+}  // namespace fba
+
+int fba_resect(fba_ctx* ctx, const fba_resect_options* o, double* eop, double* quality, int32_t* status, int64_t* n_not_ok) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_resect: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_resect between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const fba_resect_options& op = o ? *o : kResectDefaults;
+    int rc;
+    if ((rc = check_resect_options("fba_resect", op))) return rc;
+    if (c->opt.world != 1) {
+        set_error("fba_resect is single-GPU (world == 1): an image's observations are spread over the ranks");
+        return FBA_ERR_UNSUPPORTED;
+    }
+    const fba_settings& s = c->set;
+    if (op.write_xhat && !(s.est_Xc && s.est_Yc && s.est_Zc && s.est_omega && s.est_phi && s.est_kappa)) {
+        set_error("fba_resect: write_xhat with a fixed exterior orientation (an Estimate_Xc .. Estimate_Kappa flag is off)");
+        return FBA_ERR_UNSUPPORTED;
+    }
+    if ((int)c->img_ord.size() != c->L.n_img) { set_error("fba_resect: image order and layout disagree"); return FBA_ERR_ARG; }
+    if ((rc = image_list_once(c))) return rc;
+    const int64_t ni = c->L.n_img_ref;
+    const size_t no = (size_t)std::max<int64_t>(c->n_obs, 1), nio = (size_t)std::max<int64_t>(ni, 1);
+    double *d_rec = nullptr, *d_out = nullptr;
+    int32_t *d_use = nullptr, *d_st = nullptr;
+    if ((rc = ws_get(*c, WS_RESECT_REC, RESECT_REC * no, &d_rec)) || (rc = ws_get(*c, WS_RESECT_USE, no, &d_use)) ||
+        (rc = ws_get(*c, WS_RESECT_OUT, 11 * nio, &d_out)) || (rc = ws_get(*c, WS_RESECT_ST, nio, &d_st)))
+        return rc;
+    hipEvent_t e0 = c->ev[0], e1 = c->ev[1];
+    if (c->timing) (void)hipEventRecord(e0, c->stream);
+    // the camera table at d_xfull: a function of xhat alone, so between fba_accumulate and fba_solve_update it is
+    // rewritten with the values it holds (fba_intersect's argument)
+    if ((rc = launch_params(*c)) || (rc = launch_resect_gather(*c, op.use == FBA_RESECT_USE_ALL, d_rec, d_use)) ||
+        (rc = launch_resect(*c, d_rec, d_use, op.refine_iters, op.min_ratio, op.refine_tol, op.write_xhat != 0, d_out,
+                            d_out + 6 * nio, d_st)))
+        return rc;
+    if (c->timing) (void)hipEventRecord(e1, c->stream);
+    if (op.write_xhat) {  // as fba_set_xhat: neither the linearisation nor the factor belongs to the new xhat
+        c->have_lin = false;
+        c->have_delta = false;
+        c->have_factor = false;
+    }
+    std::vector<int32_t> hs;
+    if (ni > 0) {
+        if (eop) FBA_HIP(hipMemcpyAsync(eop, d_out, sizeof(double) * 6 * ni, hipMemcpyDeviceToHost, c->stream));
+        if (quality) FBA_HIP(hipMemcpyAsync(quality, d_out + 6 * nio, sizeof(double) * 5 * ni, hipMemcpyDeviceToHost, c->stream));
+        if (status || n_not_ok) {
+            hs.resize((size_t)ni);
+            FBA_HIP(hipMemcpyAsync(hs.data(), d_st, sizeof(int32_t) * ni, hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    FBA_HIP(hipStreamSynchronize(c->stream));
+    if (status) std::copy(hs.begin(), hs.end(), status);
+    if (n_not_ok) *n_not_ok = (int64_t)std::count_if(hs.begin(), hs.end(), [](int32_t v) { return v != FBA_RESECT_OK; });
+    if (c->timing) {
+        float ms = 0.f;
+        FBA_HIP(hipEventElapsedTime(&ms, e0, e1));
+        std::fill(c->last_ms, c->last_ms + 8, 0.0);
+        c->last_ms[7] = ms;
+    }
+    return FBA_OK;
+}
+
+int fba_resect_host(int32_t type, int64_t n, const double* xyz, const double* ray, const int32_t* ray_status, double cc,
+                    double ydir, double std_x, double std_y, const fba_resect_options* o, double* eop, double* quality,
+                    int32_t* status) {
+    if (type < FBA_TYPE_FISHEYE || type > FBA_TYPE_STEREOGRAPHIC) { set_error("fba_resect_host: invalid type"); return FBA_ERR_TYPE; }
+    if (n < 0 || (n > 0 && (!xyz || !ray)) || !(std_x > 0.0) || !(std_y > 0.0)) {
+        set_error("fba_resect_host: n >= 0, xyz and ray not NULL, the standard deviations > 0");
+        return FBA_ERR_ARG;
+    }
+    const fba_resect_options& op = o ? *o : kResectDefaults;
+    int rc;
+    if ((rc = check_resect_options("fba_resect_host", op))) return rc;
+    std::vector<double> rec(RESECT_REC * (size_t)n);
+    std::vector<int32_t> use((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        std::copy(ray + 5 * i, ray + 5 * i + 5, rec.begin() + RESECT_REC * i);
+        std::copy(xyz + 3 * i, xyz + 3 * i + 3, rec.begin() + RESECT_REC * i + 5);
+        use[(size_t)i] = (!ray_status || ray_status[i] == FBA_RAY_OK) ? 1 : 0;
+    }
+    const ResectHostSrc src{rec.data(), use.data(), n, cc, ydir};
+    double A[144], V[144], e[6], q[5];
+    const double zero[6] = {0, 0, 0, 0, 0, 0};
+    int st;
+    resect_solve(src, type, 1.0 / (std_x * std_x), 1.0 / (std_y * std_y), op.refine_iters, op.min_ratio, op.refine_tol, A, V,
+                 zero, e, q, st);
+    if (eop) std::copy(e, e + 6, eop);
+    if (quality) std::copy(q, q + 5, quality);
+    if (status) *status = st;
     return FBA_OK;
 }
 

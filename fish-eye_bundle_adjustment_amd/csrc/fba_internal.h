@@ -202,6 +202,7 @@ enum WsSlot : int {
     WS_COST,                // fba_cost: [4] sums, then the block partials
     WS_LM_SAVE,             // fba_adjust_lm: xhat before a trial
     WS_RAY, WS_RAY_ST, WS_RAY_XU, WS_ISECT_OUT, WS_ISECT_ST,  // fba_image_rays / fba_intersect
+    WS_RESECT_REC, WS_RESECT_USE, WS_RESECT_OUT, WS_RESECT_ST,  // fba_resect: records and flags (list order), outputs
     WS_COUNT
 };
 static_assert(WS_SEL_END - WS_SEL_Z == 10 && WS_OBS_T >= WS_SEL_END, "launch_selinv's slots run into the next name");
@@ -355,6 +356,11 @@ struct Ctx {
     double* d_pr_val = nullptr;      // [n_pres][2] p, l
     double* d_pr_out = nullptr;      // [n_prior + 1] residuals in the caller's order, then this rank's sum p v^2
     double* d_pr_part = nullptr;     // [ceil(n_pres / 256)] block partials of p v^2
+    // space resection (fba_resect; built on first use): the local observations of each image slot, ascending
+    bool have_img_list = false;
+    int32_t* d_il_start = nullptr;   // [n_img+1] list range of each image slot
+    int32_t* d_il_obs = nullptr;     // [n_obs] local observations, by image slot
+    int32_t* d_il_ext = nullptr;     // [n_img] EXT row of each slot (-1: padding) = img_ord
     double* h_pinned = nullptr;  // [HPIN_TOTAL] pinned host scratch (coherent, mapped: k_sum_parts mirrors the d_scal
                                  // slots below SCAL_MIRROR here, then HPIN_SEQ = its running count of solves)
     double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[HPIN_SEQ])
@@ -500,6 +506,9 @@ int check_inputs(const fba_problem* p, const fba_settings* s, const fba_options*
 // img_ord, img_new, full_to_ref, xfull0, tie_owner, full_owned, obs_pho, acc, gen, sched, the n_* counts, ...)
 int build_plan(const fba_problem* p, const fba_settings* s, const fba_options& opt, const fba_priors* pr,
                const PlanKnobs& knobs, Ctx& c, HostPlan& hp);
+// the observations of each image: start [n_img + 1], list [img.size()] -- a stable counting sort of the observation
+// indices by img[o] (ascending inside an image); entries of img outside [0, n_img) are left out
+void build_image_list(const std::vector<int32_t>& img, int n_img, std::vector<int32_t>& start, std::vector<int32_t>& list);
 int64_t count_unknowns(const fba_problem* p, const fba_settings* s);  // the reference's u
 void partition(const fba_problem* p, int world, std::vector<int32_t>& tie_owner, std::vector<int32_t>& ctl_owner);
 int image_order(const fba_problem* p, std::vector<int32_t>& order);   // checked camera_order
@@ -559,6 +568,13 @@ int launch_dense_awg(Ctx& c, double* dA, double* dG, const int64_t* d_map, int64
 int launch_rays(Ctx& c, double* ray, int32_t* rst, double* xu);
 int launch_intersect(Ctx& c, const double* ray, const int32_t* rst, const double* xu, int refine_iters, double min_ratio,
                      double refine_tol, bool write, double* xyz, double* qual, int32_t* st);
+// space resection (fba_resect.hip), after launch_params at d_xfull, the image list built.  launch_resect_gather: per
+// list entry the record rec [RESECT_REC] and the usable flag (use_all: tie observations too); launch_resect: per image
+// slot from those, into eop [6 n_img_ref] / qual [5 n_img_ref] / st [n_img_ref] (EXT order; every EXT image is
+// written); write: OK / REFINE images also into d_xfull's six entries
+int launch_resect_gather(Ctx& c, bool use_all, double* rec, int32_t* use);
+int launch_resect(Ctx& c, const double* rec, const int32_t* use, int refine_iters, double min_ratio, double refine_tol,
+                  bool write, double* eop, double* qual, int32_t* st);
 int border_solve_selftest(int device, const double* gram, double* coef);  // fba_test_border_solve
 
 }  // namespace fba

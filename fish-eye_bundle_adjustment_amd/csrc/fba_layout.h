@@ -28,6 +28,7 @@ constexpr int TIE_BLK = 6;       // tie point's 3 x 3 covariance block (00 01 02
 constexpr int RSD_ROW = 5;       // BuildRSD row
 constexpr int RES_ROW = 2 + RSD_ROW;  // d_res per observation: v (2) + rsd (5)
 constexpr int RAY_REC = 6;       // image ray: C, d in the object frame
+constexpr int RESECT_REC = 8;    // resection record (64 B): xu yu | d in the camera frame | X Y Z of the object point
 
 constexpr int CHUNK_OBS = 256;  // observations per k_lin_reduce / k_lin_point workgroup (chunk)
 constexpr int LR_PROF = 10;     // FBA_LR_PROFILE: 64-bit words per chunk (k_lin_reduce's stamps, fba_capi.cpp's print)

@@ -846,6 +846,18 @@ void plan_priors(Ctx& c, const Work& w, HostPlan& hp) {
 
 }  // namespace
 
+void build_image_list(const std::vector<int32_t>& img, int n_img, std::vector<int32_t>& start, std::vector<int32_t>& list) {
+    const int32_t ni = std::max(n_img, 0);
+    start.assign((size_t)ni + 1, 0);
+    for (int32_t e : img)
+        if (e >= 0 && e < ni) ++start[(size_t)e + 1];
+    for (int32_t e = 0; e < ni; ++e) start[(size_t)e + 1] += start[e];
+    list.assign((size_t)start[ni], 0);
+    std::vector<int32_t> next(start.begin(), start.end() - 1);
+    for (size_t o = 0; o < img.size(); ++o)
+        if (img[o] >= 0 && img[o] < ni) list[(size_t)next[img[o]]++] = (int32_t)o;
+}
+
 int build_plan(const fba_problem* p, const fba_settings* s, const fba_options& opt, const fba_priors* pr,
                const PlanKnobs& knobs, Ctx& c, HostPlan& hp) {
     c.prob = *p;

@@ -476,6 +476,51 @@ def read_fwd(path):
     return names, np.array(rays, dtype=np.int64), v[:, 0:3], v[:, 3:6], v[:, 6:9], words
 
 
+RSC_STATUS = ("OK", "FEW", "WEAK", "REFINE")  # FBA_RESECT_*
+
+
+def write_rsc(path, data, res):
+    """The space-resection table <Output_Filename stem>.rsc (no reference counterpart: the reference takes the
+    exterior orientation's starting values from the .ext file), tab-delimited in write_fwd's style, one row per image
+    in EXT order: imageID; points used; the resected Xc Yc Zc omega phi kappa (radians); its shift from the .ext
+    values; lambda_1 / lambda_11 of the linear solution's Gram matrix (about (relief / extent)^2; 0 for coplanar
+    points); the RMS reprojection residual in pixels of the linear and of the refined solution; and, where the status
+    is not OK, * and the status word -- FEW (fewer than 6 usable points) and WEAK (ratio below the bound): the image
+    kept its .ext values; REFINE: the linear solution was kept."""
+    if getattr(res, "resect_eop", None) is None or getattr(res, "resect_quality", None) is None or \
+            getattr(res, "resect_status", None) is None:
+        raise ValueError("write_rsc: the adjustment carries no resection (adjust(..., resect=True))")
+    eop = np.asarray(res.resect_eop, dtype=np.float64).reshape(-1, 6)
+    q = np.asarray(res.resect_quality, dtype=np.float64).reshape(-1, 5)
+    st = np.asarray(res.resect_status).reshape(-1)
+    if not (len(eop) == len(q) == len(st)) or len(eop) > len(data.EXT):
+        raise ValueError("write_rsc: one resection per image expected")
+    with open(path, "w") as fh:
+        for i in range(len(eop)):
+            row = data.EXT[i]
+            x0 = np.asarray(row[2:8], dtype=np.float64)
+            flag = [] if st[i] == 0 else ["*", RSC_STATUS[int(st[i])]]
+            fh.write("\t".join([str(row[0]), str(int(q[i, 0]))] + [_cell(v) for v in (*eop[i], *(eop[i] - x0), *q[i, 1:4])]
+                               + flag) + "\n")
+
+
+def read_rsc(path):
+    """write_rsc's table back: (imageIDs, points used (n), eop (n, 6), shift (n, 6), quality (n, 3): ratio, RMS
+    linear, RMS final; status words (n), "OK" where the row carries no flag)"""
+    names, used, vals, words = [], [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if len(c) not in (17, 19) or (len(c) == 19 and c[17] != "*"):
+                raise ValueError(f"read_rsc: {path}: expected 17 tab-separated columns, or 19 with the flag, got {len(c)}")
+            names.append(c[0])
+            used.append(int(c[1]))
+            vals.append([float(x) for x in c[2:17]])
+            words.append(c[18] if len(c) == 19 else "OK")
+    v = np.array(vals, dtype=np.float64).reshape(-1, 15)
+    return names, np.array(used, dtype=np.int64), v[:, 0:6], v[:, 6:12], v[:, 12:15], words
+
+
 def read_prr(path):
     """write_prr's table back: (names, values (n, 6): prior, std, adjusted, v, r, w -- NaN for an empty cell --,
     flagged (n) bool)"""

@@ -450,6 +450,68 @@ int fba_intersect(fba_ctx* ctx, const fba_intersect_options* o, double* xyz /*[3
                   double* quality /*[4 n_tie]: rays used, lambda_min/lambda_max, rms px linear, rms px final*/,
                   int32_t* status /*[n_tie]*/, int64_t* n_not_ok);
 
+/* Space resection: starting values of the images' exterior orientation from object points and the measured image
+ * rays (no reference counterpart: Buildxhat.m:22-63 copies the .ext rows, and main.m has no routine that derives them).
+ * Resection from control, then fba_intersect, then the adjustment starts a block from control points and measurements.
+ *
+ * The forward model is a function of the LINE through the projection centre, so for a measurement with the
+ * camera-frame direction d (fba_unproject_host's) and a known object point X the constraint d x (M (X - C)) = 0 does
+ * not depend on d's sign and is linear in the 12 entries of P = [M | -M C] (csrc/fba_resect.h):
+ *   (a) the linear solution, per image over its usable points (n of them): m their centroid, s their mean distance to
+ *       it, X~ = ((X - m) / s, 1); G = sum (I - d d') (x) (X~ X~') (12 x 12); P the eigenvector of G's smallest
+ *       eigenvalue (cyclic Jacobi), its sign such that det(P[:, :3]) > 0; M the polar factor A (A'A)^(-1/2) of
+ *       A = P[:, :3], lambda the mean singular value of A, t~ = P[:, 3] / lambda, C = m - s M' t~; the angles by
+ *       phi = asin(clamp(M20)), omega = atan2(-M21, M22), kappa = atan2(-M10, M00) (BuildAwG.m:163-165), and where
+ *       cos^2 phi = M21^2 + M22^2 <= 1e-14 (the quotients are rounding noise there): omega = 0, kappa = atan2(M01, M11).
+ *       The ratio lambda_1 / lambda_11 of G's second smallest to its largest eigenvalue measures the geometry: 0 for
+ *       coplanar points, about (relief / extent)^2 otherwise;
+ *   (b) up to refine_iters Gauss-Newton passes on the image's six unknowns alone, x <- x - N^-1 g, N = J'PJ, g = J'Pw,
+ *       w = (px - xu, py - yu) through the forward model, P = diag(1 / Meas_std^2, 1 / Meas_std_y^2) (no user weights,
+ *       no loss, no priors, no damping: contexts that carry them give the same result), N solved by Cholesky; stopped
+ *       when |dC|_inf <= refine_tol x the mean distance of C (before the pass) to the points and |d angles|_inf <=
+ *       refine_tol;
+ *   (c) the RMS reprojection residual sqrt(sum (wx^2 + wy^2) / n) in pixels at the linear and at the final solution.
+ *   A point is usable when its ray's status is FBA_RAY_OK and it belongs to the `use` class: FBA_RESECT_USE_CONTROL the
+ *   control observations (tie < 0, xyz_fixed), FBA_RESECT_USE_ALL also the tie observations at the device xhat's current
+ *   tie coordinates.  A measurement taken twice counts twice.
+ *   status per image: FBA_RESECT_OK; FBA_RESECT_FEW fewer than 6 usable points (an image without observations
+ *   included); FBA_RESECT_WEAK the ratio below min_ratio, or a NaN; FBA_RESECT_REFINE a non-positive pivot, a
+ *   non-finite value, or a final RMS above the linear one by more than 1e-9 px: the linear solution is returned.
+ *   eop [6 n_img] (EXT order): Xc Yc Zc omega phi kappa; for FEW and WEAK the image's current xhat values.  quality
+ *   [5 n_img]: points used, the ratio, RMS px linear, RMS px final, and the share of the used points with
+ *   d . M (X - C) > 0 -- 1 or 0 for a consistent solution (it tells which side W has), anything between means mirrored
+ *   geometry (FEW: n 0 0 0 0; WEAK: n, the ratio, 0 0 0).  status [n_img].  *n_not_ok: the images with a status other
+ *   than OK.  Any output pointer may be NULL.
+ *   write_xhat != 0: the OK and REFINE images replace their six entries of the device xhat (FEW and WEAK keep theirs
+ *   bit for bit), which invalidates the last linearisation and the factor as fba_set_xhat does; with any of
+ *   Estimate_Xc .. Estimate_Kappa off it returns FBA_ERR_UNSUPPORTED (a fixed exterior orientation is the user's).
+ *   Without it the call works under any flag set and leaves the context untouched: a following fba_step gives bitwise
+ *   the xhat it gives without the call.  world > 1 returns FBA_ERR_UNSUPPORTED: an image's observations are spread
+ *   over the ranks.  One GPU, plain launches on the context's stream, fixed-order sums (two calls are bitwise equal).
+ *   Not between fba_solve_update_async and fba_solve_finish (FBA_ERR_ARG).  With fba_set_timing on, fba_last_timings'
+ *   [7] afterwards holds the device time of this call's kernels, [0..6] 0.
+ * fba_resect_host (no reference counterpart; host only, no GPU): the same per-image routines on the CPU for one image,
+ *   the sums in index order: xyz [3 n] the object points, ray [5 n] fba_unproject_host's rows of their measurements,
+ *   ray_status [n] (NULL: all FBA_RAY_OK), c and ydir of the camera, the two standard deviations.  `use` and
+ *   write_xhat are ignored; for FEW and WEAK eop is zeros. */
+enum { FBA_RESECT_OK = 0, FBA_RESECT_FEW = 1, FBA_RESECT_WEAK = 2, FBA_RESECT_REFINE = 3 };
+enum { FBA_RESECT_USE_CONTROL = 0, FBA_RESECT_USE_ALL = 1 };
+typedef struct fba_resect_options {
+    int32_t use;           /* CONTROL: control observations only (tie < 0, xyz_fixed); ALL: also tie
+                              observations, at the device xhat's current tie coordinates */
+    int32_t refine_iters;  /* 0: linear only; default (NULL options) 10 */
+    int32_t write_xhat;    /* != 0: OK / REFINE images replace their six EOP entries of the device xhat */
+    int32_t reserved;
+    double  min_ratio;     /* default 1e-6 */
+    double  refine_tol;    /* default 1e-10 */
+} fba_resect_options;
+int fba_resect(fba_ctx* ctx, const fba_resect_options* o, double* eop /*[6 n_img], EXT order*/,
+               double* quality /*[5 n_img]*/, int32_t* status /*[n_img]*/, int64_t* n_not_ok);
+int fba_resect_host(int32_t type, int64_t n, const double* xyz /*[3n]*/,
+                    const double* ray /*[5n]: xu yu d, fba_unproject_host's rows*/,
+                    const int32_t* ray_status /*[n] or NULL*/, double c, double ydir, double std_x, double std_y,
+                    const fba_resect_options* o, double* eop /*[6]*/, double* quality /*[5]*/, int32_t* status);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
