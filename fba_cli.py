@@ -11,6 +11,10 @@
     ... main <folder> ... --resect[=control|all]  the images' starting values by space resection from their control
                                                points (all: and the tie points at their .cnt coordinates) instead of
                                                the .ext values; also writes the .rsc table (report.write_rsc)
+    ... main <folder> ... --vce[=xy|camera|camera_xy]  variance components of the image measurements per axis (the
+                                               default), per camera or per camera and axis, estimated and applied
+                                               on the device before the post-fit outputs; also writes the .vce table
+                                               (report.write_vce); not together with --robust
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
     ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
                                                of sigma (default: the 95 %-efficiency constants, huber 1.345,

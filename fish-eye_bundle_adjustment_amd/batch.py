@@ -134,6 +134,23 @@ def parse_resect(args):
     return rest, resect
 
 
+def parse_vce(args):
+    """--vce, --vce=xy, --vce=camera or --vce=camera_xy anywhere in args -> (args without it, None or the grouping;
+    a bare --vce is "xy"): variance components of the image measurements' groups (`main` only; writes the .vce table).
+    ValueError for another grouping."""
+    rest, vce = [], None
+    for a in args:
+        if a == "--vce":
+            vce = "xy"
+        elif a.startswith("--vce="):
+            vce = a.split("=", 1)[1].lower()
+            if vce not in ("xy", "camera", "camera_xy"):
+                raise ValueError("--vce: xy, camera or camera_xy")
+        else:
+            rest.append(a)
+    return rest, vce
+
+
 def parse_robust(args):
     """--robust huber[:k] | cauchy[:k] (also --robust=...) anywhere in args -> (args without it, loss or None,
     k or None).  ValueError for a missing or unknown loss, or a k that is not a positive number."""
@@ -165,13 +182,13 @@ def parse_robust(args):
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
     anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors', --lm parse_lm's)"""
-    args = parse_resect(args)[0]
+    args = parse_vce(parse_resect(args)[0])[0]
     args = parse_intersect(parse_ellipsoids(parse_lm(parse_priors(parse_robust(args)[0])[0])[0])[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--resect[=control|all]] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--resect[=control|all]] [--vce[=xy|camera|camera_xy]] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
          "batch <folder>... [--robust LOSS[:k]] [--priors] [--lm[=lambda0]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
          "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
          "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
@@ -182,7 +199,9 @@ USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] 
          "points' starting values by forward intersection of their image rays instead of the .cnt\n      coordinates; "
          "writes the .fwd table\n  --resect[=control|all]  (main) the images' starting values by space resection from their control "
          "points (all: and\n      the tie points at their .cnt coordinates) instead of the .ext values; writes the .rsc "
-         "table")
+         "table\n  --vce[=xy|camera|camera_xy]  (main) variance components of the image measurements per axis, per camera or "
+         "per camera and\n      axis, estimated and applied before the post-fit outputs (not with --robust); writes the "
+         ".vce table")
 
 
 def cli(argv=None):
@@ -196,6 +215,9 @@ def cli(argv=None):
         argv, ellipsoids = parse_ellipsoids(argv)
         argv, intersect = parse_intersect(argv)
         argv, resect = parse_resect(argv)
+        argv, vce = parse_vce(argv)
+        if vce and robust:
+            raise ValueError("--vce cannot be combined with --robust")
     except ValueError as e:
         print(f"Error: {e}")
         print(USAGE)
@@ -205,7 +227,8 @@ def cli(argv=None):
         folder, plot, reliability = parse_main(argv[1:])
         return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors),
                     **_lm_kw(lm), **({"ellipsoids": True} if ellipsoids else {}),
-                    **({"intersect": True} if intersect else {}), **({"resect": resect} if resect else {}))
+                    **({"intersect": True} if intersect else {}), **({"resect": resect} if resect else {}),
+                    **({"vce": vce} if vce else {}))
     if len(argv) >= 2 and argv[0] == "batch":
         done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors), **({"lm": lm} if lm else {}))
         return 1 if any(e for _, e in done) else 0

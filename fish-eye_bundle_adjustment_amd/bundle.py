@@ -108,6 +108,17 @@ class Adjustment:
     resect_eop: np.ndarray = None      # (n_img, 6)
     resect_quality: np.ndarray = None  # (n_img, 5)
     resect_status: np.ndarray = None   # (n_img)
+    # variance component estimation (vce=...): per group (then the rows of no group, then the priors: reported only)
+    # the cumulative variance factor relative to the starting weights, the a-posteriori standard deviation
+    # sqrt(component) x Meas_std in pixels (Meas_std_y for a group of y rows only; nan for the two report entries), the
+    # per-round table [R, T, n, sigma2], FBA_VCE_* of the last round (capi.VCE_STATUS), the rounds and the names
+    vce_component: np.ndarray = None   # (n_groups + 2)
+    vce_sigma: np.ndarray = None       # (n_groups + 2)
+    vce_table: np.ndarray = None       # (rounds, n_groups + 2, 4)
+    vce_status: np.ndarray = None      # (n_groups + 2)
+    vce_rounds: int = None
+    vce_names: list = None
+    vce_converged: bool = None
 
 
 def _priors_of(data, priors):
@@ -132,9 +143,38 @@ def prior_statistics(sigma02, cx_diag, index, sigma, v):
     return r, np.where(ok, v / (sigma * np.sqrt(np.where(ok, r, 1.0))), 0.0)
 
 
+def vce_groups(packed, vce):
+    """adjust()'s vce argument -> (group (2 n_pts) int32, names): "xy" one group per axis, "camera" one per camera,
+    "camera_xy" one per camera and axis, or (group_array, names) as given (ids in [0, len(names)) or -1)"""
+    n = packed.n_pts
+    cam = np.asarray(packed.cam, dtype=np.int32)
+    g = np.zeros((n, 2), dtype=np.int32)
+    if isinstance(vce, str):
+        if vce == "xy":
+            g[:, 1] = 1
+            names = ["x", "y"]
+        elif vce == "camera":
+            g[:] = cam[:, None]
+            names = [f"cam{k}" for k in range(packed.n_cam)]
+        elif vce == "camera_xy":
+            g[:, 0], g[:, 1] = 2 * cam, 2 * cam + 1
+            names = [f"cam{k}.{a}" for k in range(packed.n_cam) for a in "xy"]
+        else:
+            raise ValueError(f"adjust: unknown vce {vce!r} (\"xy\", \"camera\", \"camera_xy\" or (group, names))")
+        return g.reshape(-1), names
+    try:
+        arr, names = vce
+    except (TypeError, ValueError):
+        raise ValueError("adjust: vce must be \"xy\", \"camera\", \"camera_xy\" or (group_array, names)") from None
+    g = np.ascontiguousarray(arr, dtype=np.int32).reshape(-1)
+    if g.size != 2 * n:
+        raise ValueError("adjust: the vce group array must have 2*n_pts entries")
+    return g, [str(x) for x in names]
+
+
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
            reliability=False, priors=None, method="gn", lm_options=None, point_precision=False,
-           intersect=False, resect=False) -> Adjustment:
+           intersect=False, resect=False, vce=None, vce_options=None) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -175,7 +215,17 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     replaces its .ext starting values; "all" also uses the tie observations at their .cnt coordinates.  An image
     with fewer than six usable points or points too close to a plane keeps its .ext values.  With intersect=True
     the chain resection, intersection, adjustment starts a block from control points and measurements alone.
-    Adjustment.resect_eop, resect_quality and resect_status carry the result."""
+    Adjustment.resect_eop, resect_quality and resect_status carry the result.
+
+    vce (no reference counterpart: main.m:397-402 fixes the weights): "xy", "camera", "camera_xy" or (group_array,
+    names) -- variance component estimation over groups of image measurements (fba_vce; vce_options: a dict of
+    capi.Context.vce's max_rounds, tol, min_redundancy, clip).  It runs after resect / intersect; with method="lm"
+    after the damped loop, otherwise in place of the plain loop.  sigma0^2, Cx, the reliability numbers and the
+    ellipsoids then come from the re-weighted last pass, Adjustment.weights holds the weights and Adjustment.vce_*
+    the components.  Priors keep their stated accuracy: the groups are estimated relative to it.  Together with
+    robust= it raises ValueError (the loss factor and a variance component would fight over the same residuals)."""
+    if vce is not None and robust:
+        raise ValueError("adjust: vce together with robust is not supported")
     if resect not in (False, None, True, "control", "all"):
         raise ValueError(f"adjust: unknown resect {resect!r} (True, \"control\" or \"all\")")
     if method not in ("gn", "lm"):
@@ -197,8 +247,23 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         if method == "lm":
             nt, npol, lmh = ctx.adjust_lm(lm_options)
             it, hist = nt + npol, lmh[:, 2].copy()
-        else:
+        elif vce is None:
             it, hist = ctx.adjust()
+        else:
+            it, hist = 0, np.zeros(0)
+        vkw = {}
+        if vce is not None:
+            grp, names = vce_groups(ctx.packed, vce)
+            vr = ctx.vce(grp, len(names), **(vce_options or {}))
+            it += vr["iterations"]
+            std = np.full(len(names) + 2, np.nan)
+            for gi in range(len(names)):
+                rows = np.nonzero(grp == gi)[0]
+                only_y = rows.size > 0 and bool(np.all(rows % 2 == 1))
+                std[gi] = float(ctx.settings.meas_std_y if only_y else ctx.settings.meas_std_x)
+            vkw = dict(vce_component=vr["component"], vce_sigma=np.sqrt(vr["component"]) * std, vce_table=vr["table"],
+                       vce_status=vr["status"], vce_rounds=vr["rounds"], vce_names=names + ["(no group)", "(priors)"],
+                       vce_converged=vr["converged"])
         if robust:
             ctx.set_loss(robust, robust_k)
             cap, thr = max(int(ctx.settings.iteration_cap), 1), float(ctx.settings.threshold)
@@ -210,7 +275,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         t1 = time.perf_counter()
         xhat = ctx.get_xhat()
         v, rsd, st = ctx.residuals()
-        eff = ctx.get_weights() if (weights is not None or robust) else None
+        eff = ctx.get_weights() if (weights is not None or robust or vce is not None) else None
         red = wst = None
         ppk = {}
         if point_precision:
@@ -230,7 +295,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk, **ikw)
+                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk, **ikw, **vkw)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -256,11 +321,13 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_fwd(os.path.join(folder, name + ".fwd"), data, res)
     if getattr(res, "resect_status", None) is not None:
         report.write_rsc(os.path.join(folder, name + ".rsc"), data, res)
+    if getattr(res, "vce_component", None) is not None:
+        report.write_vce(os.path.join(folder, name + ".vce"), res)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False, resect=False) -> int:
+         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False, resect=False, vce=None) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
@@ -271,7 +338,9 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
     adjust()'s point_precision; the .ell table (report.write_ell) is written too.  intersect=True: adjust()'s
     intersect -- the tie points' starting values from their image rays instead of the .cnt file; the .fwd table
     (report.write_fwd) is written too.  resect=True / "control" / "all": adjust()'s resect -- the images' starting
-    values by space resection instead of the .ext file; the .rsc table (report.write_rsc) is written too."""
+    values by space resection instead of the .ext file; the .rsc table (report.write_rsc) is written too.
+    vce="xy" / "camera" / "camera_xy": adjust()'s vce -- variance components of the image measurements' groups; the
+    .vce table (report.write_vce) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
@@ -281,6 +350,7 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
                      **({"point_precision": True} if ellipsoids else {}),
                      **({"intersect": True} if intersect else {}),
                      **({"resect": resect} if resect else {}),
+                     **({"vce": vce} if vce else {}),
                      **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:

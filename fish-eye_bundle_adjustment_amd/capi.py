@@ -23,6 +23,8 @@ RAY_STATUS = ("ok", "domain")                    # FBA_RAY_*
 ISECT_STATUS = ("ok", "few", "weak", "refine")   # FBA_ISECT_*
 RESECT_STATUS = ("ok", "few", "weak", "refine")  # FBA_RESECT_*
 RESECT_USE = ("control", "all")                  # FBA_RESECT_USE_*
+VCE_STATUS = ("ok", "empty", "weak", "clipped")  # FBA_VCE_*
+VCE_MAX_GROUPS = 256                             # FBA_VCE_MAX_GROUPS
 
 # every symbol include/fba.h declares
 EXPORTS = (
@@ -37,6 +39,7 @@ EXPORTS = (
     "fba_postfit_outputs",
     "fba_unproject_host", "fba_image_rays", "fba_intersect",
     "fba_resect", "fba_resect_host",
+    "fba_vce", "fba_vce_host",
 )
 # ... but for the host-only helpers whose names carry a digit (tests/test_damping_host.py reads the header's
 # declarations with a letters-only pattern and compares them with EXPORTS)
@@ -107,6 +110,15 @@ class ResectOptions(C.Structure):
                 raise ValueError(f"resect: unknown use {use!r} (one of {', '.join(RESECT_USE)})")
             use = RESECT_USE.index(use.lower())
         super().__init__(int(use), int(refine_iters), int(bool(write_xhat)), 0, float(min_ratio), float(refine_tol))
+
+
+class VceOptions(C.Structure):
+    """fba_vce_options; the defaults are the library's (a NULL pointer)"""
+    _fields_ = [("max_rounds", C.c_int32), ("reserved", C.c_int32), ("tol", C.c_double),
+                ("min_redundancy", C.c_double), ("clip", C.c_double)]
+
+    def __init__(self, max_rounds=10, tol=1e-3, min_redundancy=1.0, clip=100.0):
+        super().__init__(int(max_rounds), 0, float(tol), float(min_redundancy), float(clip))
 
 
 def pack_priors(priors):
@@ -180,6 +192,8 @@ def _load():
         "fba_intersect": ([P, P, P, P, P, P], C.c_int),
         "fba_resect": ([P, P, P, P, P, P], C.c_int),
         "fba_resect_host": ([I, C.c_int64, P, P, P, D, D, D, D, P, P, P, P], C.c_int),
+        "fba_vce": ([P, I, P, P, P, P, P, P, P, P], C.c_int),
+        "fba_vce_host": ([C.c_int64, I, P, P, P, P, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -518,6 +532,29 @@ class Context:
         check(lib.fba_resect(self.h, C.byref(op), ptr(eop), ptr(q), ptr(st), C.byref(bad)))
         return eop[:ni], q[:ni], st[:ni], bad.value
 
+    def vce(self, group, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0, clip=100.0):
+        """fba_vce: variance components of groups of image measurements, estimated and applied on the device.
+        group: (2 n_pts) ids in [0, n_groups) or -1 (no estimated group), PHO order, x y interleaved like v (or
+        (n_pts, 2)).  Returns a dict: component (n_groups + 2) the cumulative variance factor of each group relative to
+        its starting weights (the last two entries -- the rows with id -1, the priors -- are reported only and stay
+        1); table (rounds, n_groups + 2, 4): R, T, n and sigma2 of every round; status (n_groups + 2) FBA_VCE_*
+        (capi.VCE_STATUS) of the last round; rounds, iterations, converged.  Afterwards the context is as adjust()
+        leaves one with these weights: residuals(), postfit() and get_weights() work unchanged.  One GPU, no robust
+        loss, no damping."""
+        g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+        if g.size != 2 * self.packed.n_pts:
+            raise ValueError("vce: group must have 2*n_pts entries")
+        op = VceOptions(max_rounds, tol, min_redundancy, clip)
+        ng2 = max(int(n_groups), 0) + 2
+        comp = np.zeros(ng2)
+        table = np.zeros((max(int(max_rounds), 1), ng2, 4))
+        st = np.zeros(ng2, dtype=np.int32)
+        rounds, its, conv = C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib.fba_vce(self.h, int(n_groups), ptr(g), C.byref(op), ptr(comp), ptr(table), ptr(st), C.byref(rounds),
+                          C.byref(its), C.byref(conv)))
+        return {"component": comp, "table": table[: rounds.value].copy(), "status": st, "rounds": rounds.value,
+                "iterations": its.value, "converged": bool(conv.value)}
+
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""
         check(lib.fba_set_spin_bound(self.h, int(spins)))
@@ -589,6 +626,25 @@ def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, r
                               float(c), float(ydir), float(std_x), float(std_y), C.byref(op), ptr(eop), ptr(q),
                               C.byref(st)))
     return eop, q, st.value
+
+
+def vce_host(group, r, t, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0, clip=100.0):
+    """fba_vce_host: the device's group arithmetic (csrc/fba_vce.h) run on the CPU, no GPU needed: the sums of r and t
+    over the rows of each group in index order, then the estimate, the clamp, the factor and the status.  group (n)
+    ids in [0, n_groups) or -1 -> (sums (n_groups + 1, 3): R T n, the last row the ids -1; sigma2, factor, status
+    (n_groups))."""
+    g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
+    r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+    if not (g.size == r.size == t.size):
+        raise ValueError("vce_host: group, r and t must have the same length")
+    op = VceOptions(max_rounds, tol, min_redundancy, clip)
+    ng = max(int(n_groups), 0)
+    sums, s2, f, st = np.zeros((ng + 1, 3)), np.zeros(max(ng, 1)), np.zeros(max(ng, 1)), np.zeros(max(ng, 1), dtype=np.int32)
+    n = g.size
+    check(lib.fba_vce_host(n, int(n_groups), ptr(g) if n else None, ptr(r) if n else None, ptr(t) if n else None,
+                           C.byref(op), ptr(sums), ptr(s2), ptr(f), ptr(st)))
+    return sums, s2[:ng], f[:ng], st[:ng]
 
 
 def tie_blocks(cx_tie):

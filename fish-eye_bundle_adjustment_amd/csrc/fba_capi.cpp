@@ -24,6 +24,7 @@
 #include "fba_eig3.h"
 #include "fba_ray.h"
 #include "fba_resect.h"
+#include "fba_vce.h"
 
 namespace fba {
 
@@ -1444,6 +1445,208 @@ int fba_resect_host(int32_t type, int64_t n, const double* xyz, const double* ra
     if (eop) std::copy(e, e + 6, eop);
     if (quality) std::copy(q, q + 5, quality);
     if (status) *status = st;
+    return FBA_OK;
+}
+
+// ---- variance component estimation over observation groups (no reference counterpart) ----
+namespace fba {
+static const fba_vce_options kVceDefaults{10, 0, 1e-3, 1.0, 100.0};
+static int check_vce_args(const char* who, int64_t n_rows, int32_t n_groups, const int32_t* group, const fba_vce_options& op) {
+    char buf[200];
+    if (n_groups < 1 || n_groups > FBA_VCE_MAX_GROUPS) {
+        snprintf(buf, sizeof buf, "%s: n_groups = %d outside [1, %d]", who, (int)n_groups, FBA_VCE_MAX_GROUPS);
+        set_error(buf);
+        return FBA_ERR_ARG;
+    }
+    if (op.max_rounds < 1 || !std::isfinite(op.tol) || op.tol < 0.0 || !std::isfinite(op.min_redundancy) ||
+        op.min_redundancy < 0.0 || !std::isfinite(op.clip) || op.clip < 1.0) {
+        set_error(std::string(who) + ": max_rounds >= 1; tol >= 0, min_redundancy >= 0 and clip >= 1, all finite");
+        return FBA_ERR_ARG;
+    }
+    if (n_rows < 0 || (n_rows > 0 && !group)) { set_error(std::string(who) + ": NULL group array"); return FBA_ERR_ARG; }
+    for (int64_t i = 0; i < n_rows; ++i)
+        if (group[i] < -1 || group[i] >= n_groups) {
+            snprintf(buf, sizeof buf, "%s: group[%ld] = %d outside [-1, %d)", who, (long)i, (int)group[i], (int)n_groups);
+            set_error(buf);
+            return FBA_ERR_ARG;
+        }
+    return FBA_OK;
+}
+}  // namespace fba
+
+int fba_vce(fba_ctx* ctx, int32_t n_groups, const int32_t* group, const fba_vce_options* o, double* component, double* table,
+            int32_t* status, int32_t* rounds, int32_t* iterations, int32_t* converged) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_vce: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_vce between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const fba_vce_options& op = o ? *o : kVceDefaults;
+    int rc;
+    if ((rc = check_vce_args("fba_vce", 2 * c->n_pts, n_groups, group, op))) return rc;
+    if (c->opt.world != 1) { set_error("fba_vce is single-GPU (world == 1)"); return FBA_ERR_UNSUPPORTED; }
+    if (c->loss != FBA_LOSS_NONE) {
+        set_error("fba_vce with a robust loss set: its IRLS factor and a variance component would fight over the same residuals");
+        return FBA_ERR_UNSUPPORTED;
+    }
+    if (c->damp_on()) { set_error("fba_vce with damping > 0: the factor of a damped solve is not that of N"); return FBA_ERR_UNSUPPORTED; }
+
+    const Layout& L = c->L;
+    const int ng = n_groups, ng1 = ng + 1, ng2 = ng + 2;
+    const int64_t n_blocks = (c->n_obs + 255) / 256;
+    // the group ids in local order, once per call
+    std::vector<int32_t> gl(2 * (size_t)std::max<int64_t>(c->n_obs, 1), -1);
+    for (int64_t i = 0; i < c->n_obs; ++i) {
+        gl[2 * i] = group[2 * c->obs_pho[i]];
+        gl[2 * i + 1] = group[2 * c->obs_pho[i] + 1];
+    }
+    int32_t* d_grp = nullptr;
+    double *d_slab = nullptr, *d_out = nullptr, *d_q = nullptr, *d_cdiag = nullptr, *d_pdiag = nullptr;
+    if ((rc = ws_get(*c, WS_VCE_GROUP, gl.size(), &d_grp)) ||
+        (rc = ws_get(*c, WS_VCE_SLAB, (size_t)std::max<int64_t>(n_blocks, 1) * ng1 * VCE_SUMS, &d_slab)) ||
+        (rc = ws_get(*c, WS_VCE_OUT, (size_t)ng1 * VCE_OUT, &d_out)) ||
+        (rc = ws_get(*c, WS_REL_Q, 2 * (size_t)std::max<int64_t>(c->n_obs, 1), &d_q)))
+        return rc;
+    std::vector<int64_t> pr_idx;
+    std::vector<double> pr_val, cd, pd;
+    if (c->n_prior > 0) {  // (world == 1: this rank adds every prior)
+        if ((rc = ws_get(*c, WS_CDIAG, (size_t)L.u_c, &d_cdiag)) || (rc = ws_get(*c, WS_PDIAG, 3 * (size_t)std::max(L.n_tie, 1), &d_pdiag)))
+            return rc;
+        pr_idx.resize(2 * (size_t)c->n_pres);
+        pr_val.resize(2 * (size_t)c->n_pres);
+        cd.resize((size_t)L.u_c);
+        pd.resize(3 * (size_t)L.n_tie);
+        if (c->n_pres > 0) {
+            FBA_HIP(hipMemcpy(pr_idx.data(), c->d_pr_idx, sizeof(int64_t) * pr_idx.size(), hipMemcpyDeviceToHost));
+            FBA_HIP(hipMemcpy(pr_val.data(), c->d_pr_val, sizeof(double) * pr_val.size(), hipMemcpyDeviceToHost));
+        }
+    }
+    FBA_HIP(hipMemcpyAsync(d_grp, gl.data(), sizeof(int32_t) * gl.size(), hipMemcpyHostToDevice, c->stream));
+    FBA_HIP(hipStreamSynchronize(c->stream));  // (gl is pageable memory of this call)
+
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // events of the call's own: the steps in between use the context's
+    if (c->timing) {
+        FBA_HIP(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("fba_vce: hipEventCreate failed"); return FBA_ERR_HIP; }
+    }
+    struct EvGuard {
+        hipEvent_t a, b;
+        ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } guard{e0, e1};
+
+    std::vector<double> comp((size_t)ng2, 1.0), out((size_t)ng1 * VCE_OUT);
+    std::vector<int32_t> st((size_t)ng2, FBA_VCE_EMPTY);
+    int n_rounds = 0, n_iter = 0, conv = 0;
+    double own_ms = 0.0;
+    auto publish = [&]() {
+        if (component) std::copy(comp.begin(), comp.end(), component);
+        if (status) std::copy(st.begin(), st.end(), status);
+        if (rounds) *rounds = n_rounds;
+        if (iterations) *iterations = n_iter;
+        if (converged) *converged = conv;
+        if (c->timing) {
+            std::fill(c->last_ms, c->last_ms + 8, 0.0);
+            c->last_ms[7] = own_ms;
+        }
+    };
+    for (int k = 0; k < op.max_rounds; ++k) {
+        int32_t it = 0;
+        rc = fba_adjust(ctx, &it, nullptr);
+        n_iter += it;
+        if (rc) { publish(); return rc; }
+        if (!c->have_factor || !c->have_delta) { publish(); set_error("fba_vce: the last solve left no factor"); return FBA_ERR_ARG; }
+        if (c->timing) (void)hipEventRecord(e0, c->stream);
+        if ((rc = launch_vce_q(*c, d_cdiag, d_pdiag, d_q)) ||
+            (rc = launch_vce_sums(*c, d_q, d_grp, ng, op.min_redundancy, op.clip, d_slab, d_out))) {
+            publish();
+            return rc;
+        }
+        if (c->timing) (void)hipEventRecord(e1, c->stream);
+        FBA_HIP(hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+        if (c->n_prior > 0) {
+            FBA_HIP(hipMemcpyAsync(cd.data(), d_cdiag, sizeof(double) * cd.size(), hipMemcpyDeviceToHost, c->stream));
+            if (!pd.empty()) FBA_HIP(hipMemcpyAsync(pd.data(), d_pdiag, sizeof(double) * pd.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        FBA_HIP(hipStreamSynchronize(c->stream));
+        if (c->timing) {
+            float ms = 0.f;
+            FBA_HIP(hipEventElapsedTime(&ms, e0, e1));
+            own_ms += ms;
+        }
+        n_rounds = k + 1;
+        // the round's rows: the groups and the rows of no group from the device, the priors on the host
+        double* trow = table ? table + (size_t)k * ng2 * 4 : nullptr;
+        bool finite = true, clipped = false, within = true;
+        for (int g = 0; g < ng1; ++g) {
+            const double* r = out.data() + (size_t)VCE_OUT * g;
+            st[g] = (int32_t)r[5];
+            if (trow) { trow[4 * g] = r[0]; trow[4 * g + 1] = r[1]; trow[4 * g + 2] = r[2]; trow[4 * g + 3] = r[3]; }
+            finite = finite && std::isfinite(r[0]) && std::isfinite(r[1]);
+            if (g < ng) {
+                clipped = clipped || st[g] == FBA_VCE_CLIPPED;
+                if (st[g] == FBA_VCE_OK && !(std::fabs(r[3] - 1.0) <= op.tol)) within = false;
+            }
+        }
+        double pR = 0.0, pT = 0.0;
+        if (c->n_prior > 0) {
+            for (int64_t j = 0; j < c->n_pres; ++j) {
+                const int64_t i = pr_idx[2 * j];
+                pR += 1.0 - pr_val[2 * j] * (i < L.u_c ? cd[(size_t)i] : pd[(size_t)(i - L.u_c)]);
+            }
+            if ((rc = fba_get_priors(ctx, nullptr, nullptr, &pT))) { publish(); return rc; }
+            finite = finite && std::isfinite(pR) && std::isfinite(pT);
+        }
+        st[ng1] = c->n_prior > 0 ? FBA_VCE_OK : FBA_VCE_EMPTY;
+        if (trow) {
+            trow[4 * ng1] = pR; trow[4 * ng1 + 1] = pT; trow[4 * ng1 + 2] = (double)c->n_prior;
+            trow[4 * ng1 + 3] = (c->n_prior > 0 && pR > 0.0) ? pT / pR : 1.0;
+        }
+        if (!finite) {
+            publish();
+            set_error("fba_vce: a non-finite group sum in round " + std::to_string(k + 1));
+            return FBA_ERR_NONFINITE;
+        }
+        conv = (within && !clipped) ? 1 : 0;
+        if (conv || k == op.max_rounds - 1) break;
+        // re-weight: the first rescale of an unweighted context switches the weighted kernels on
+        const bool first = !c->weights_on;
+        if (first) {
+            if ((rc = weight_buffers(c)) || (rc = weighting_changed(c))) { publish(); return rc; }
+        }
+        if ((rc = launch_vce_rescale(*c, d_grp, d_out, ng, first))) { publish(); return rc; }
+        FBA_HIP(hipStreamSynchronize(c->stream));
+        c->weights_on = true;
+        c->have_lin = false;  // neither the linearisation nor the factor belongs to the new weights
+        c->have_factor = false;
+        for (int g = 0; g < ng; ++g) comp[g] *= out[(size_t)VCE_OUT * g + 3];
+    }
+    // one plain step: the context as the loop leaves one with these weights (lin, delta, factor)
+    double dsum = 0.0;
+    rc = fba_step(ctx, &dsum);
+    ++n_iter;
+    publish();
+    return rc;
+}
+
+int fba_vce_host(int64_t n_rows, int32_t n_groups, const int32_t* group, const double* r, const double* t,
+                 const fba_vce_options* o, double* sums, double* sigma2, double* factor, int32_t* status) {
+    const fba_vce_options& op = o ? *o : kVceDefaults;
+    int rc;
+    if ((rc = check_vce_args("fba_vce_host", n_rows, n_groups, group, op))) return rc;
+    if (n_rows > 0 && (!r || !t)) { set_error("fba_vce_host: NULL r or t"); return FBA_ERR_ARG; }
+    std::vector<double> s((size_t)(n_groups + 1) * VCE_SUMS, 0.0);
+    vce_sum_rows(n_rows, n_groups, group, r, t, s.data());
+    if (sums) std::copy(s.begin(), s.end(), sums);
+    bool finite = true;
+    for (int g = 0; g <= n_groups; ++g) {
+        finite = finite && std::isfinite(s[(size_t)VCE_SUMS * g]) && std::isfinite(s[(size_t)VCE_SUMS * g + 1]);
+        if (g == n_groups) break;
+        double e, f;
+        int st;
+        vce_group(s[(size_t)VCE_SUMS * g], s[(size_t)VCE_SUMS * g + 1], s[(size_t)VCE_SUMS * g + 2], op.min_redundancy, op.clip, e, f, st);
+        if (sigma2) sigma2[g] = e;
+        if (factor) factor[g] = f;
+        if (status) status[g] = st;
+    }
+    if (!finite) { set_error("fba_vce_host: a non-finite group sum"); return FBA_ERR_NONFINITE; }
     return FBA_OK;
 }
 

@@ -753,4 +753,18 @@ int launch_postfit(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_iblk, con
     return FBA_OK;
 }
 
+// fba_vce's share of the post-fit driver: the selected inverse, the cofactor diagonals when the context has priors
+// (d_cdiag [u_c], d_pdiag [3 n_tie]; nullptr: not wanted) and q per local observation (launch_rel_q), without
+// k_rel_finish's scatter.  Consumes the factor like launch_postfit; the caller synchronises
+int launch_vce_q(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_q) {
+    SelInv si;
+    int rc;
+    if (d_pdiag) FBA_HIP(hipMemsetAsync(d_pdiag, 0, sizeof(double) * 3 * std::max(c.L.n_tie, 1), c.stream));
+    if ((rc = launch_selinv(c, si)) || (d_cdiag && (rc = launch_cov_outputs(c, si, d_cdiag, d_pdiag, nullptr, nullptr, nullptr, 0))) ||
+        (rc = launch_rel_q(c, si, d_q)))
+        return rc;
+    c.have_factor = false;
+    return FBA_OK;
+}
+
 }  // namespace fba

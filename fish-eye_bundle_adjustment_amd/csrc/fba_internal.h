@@ -203,6 +203,7 @@ enum WsSlot : int {
     WS_LM_SAVE,             // fba_adjust_lm: xhat before a trial
     WS_RAY, WS_RAY_ST, WS_RAY_XU, WS_ISECT_OUT, WS_ISECT_ST,  // fba_image_rays / fba_intersect
     WS_RESECT_REC, WS_RESECT_USE, WS_RESECT_OUT, WS_RESECT_ST,  // fba_resect: records and flags (list order), outputs
+    WS_VCE_GROUP, WS_VCE_SLAB, WS_VCE_OUT,  // fba_vce: group ids (local order), block partial sums, the groups' rows
     WS_COUNT
 };
 static_assert(WS_SEL_END - WS_SEL_Z == 10 && WS_OBS_T >= WS_SEL_END, "launch_selinv's slots run into the next name");
@@ -552,7 +553,17 @@ struct SelInv {
     int nz = 0;
 };
 int launch_selinv(Ctx& c, SelInv& si);
-int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst);  // fba_rel.hip
+int launch_rel_q(Ctx& c, SelInv& si, double* d_q);  // fba_rel.hip: v into d_res, q = a Cx a' per local row into d_q
+int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst);  // launch_rel_q + k_rel_finish
+// variance component estimation (fba_vce.hip).  launch_vce_q (fba_cov.hip): selected inverse, the cofactor diagonals
+// (nullptr: none) and launch_rel_q, consuming the factor.  launch_vce_sums: the group sums of the local rows and the
+// groups' rows [n_groups + 1][VCE_OUT] (R T n sigma2 factor status; row n_groups: the rows of no group) into d_out;
+// d_grp [2 n_obs] group ids in local order, d_slab [ceil(n_obs / 256)][n_groups + 1][VCE_SUMS].  launch_vce_rescale:
+// d_sw *= the factors of d_out (first: d_sw = the factors)
+int launch_vce_q(Ctx& c, double* d_cdiag, double* d_pdiag, double* d_q);
+int launch_vce_sums(Ctx& c, const double* d_q, const int32_t* d_grp, int n_groups, double min_redundancy, double clip,
+                    double* d_slab, double* d_out);
+int launch_vce_rescale(Ctx& c, const int32_t* d_grp, const double* d_out, int n_groups, bool first);
 // the post-fit driver (fba_cov.hip) of fba_covariance, fba_reliability and fba_postfit_outputs: the covariance and
 // the reliability outputs on one selected inverse, plus the tie points' full 3 x 3 blocks sigma02 Cx_pp (d_blk
 // [TIE_BLK n_tie]; k_cov_pts_blk, k_cov_gen_blk) and their ellipsoids (d_ell [ELL_OUT n_tie]; k_ellipsoid);

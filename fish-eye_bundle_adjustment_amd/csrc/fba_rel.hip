@@ -304,16 +304,14 @@ __global__ __launch_bounds__(256) void k_rel_finish(const double* __restrict__ q
 
 int launch_obs_T(Ctx& c, double* T);
 
-// after launch_selinv (and launch_cov_outputs, which shares d_T): q per local observation into d_q
-// [2 n_obs], then r and w in PHO order into d_red / d_wst [2 n_pts] (zeroed first: another rank's rows).
-// Runs launch_residuals for v, so c.d_res / c.d_part are overwritten (fba_residuals recomputes both).
-int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst) {
+// after launch_selinv (and launch_cov_outputs, which shares d_T): v of the last linearisation into c.d_res and
+// q = a Cx a' per local observation into d_q [2 n_obs] (local order) -- the part of the reliability outputs that
+// fba_vce shares.  Runs launch_residuals for v, so c.d_res / c.d_part are overwritten (fba_residuals recomputes both).
+int launch_rel_q(Ctx& c, SelInv& si, double* d_q) {
     const Layout& L = c.L;
     const GenPlan& g = c.gen;
     int rc;
     const RelMat M{c.d_S, L.ld, si.d_Z, si.d_Wz, si.nz, L.n_pad};
-    FBA_HIP(hipMemsetAsync(d_red, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
-    FBA_HIP(hipMemsetAsync(d_wst, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
     if (c.n_obs == 0) return FBA_OK;
     if ((rc = launch_residuals(c))) return rc;  // v of the last linearisation (d_J) and correction, as fba_residuals
     if (c.n_lp > 0) {
@@ -333,6 +331,16 @@ int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d
                                                          L.cw, d_Xg, d_q);
     }
     FBA_HIP(hipGetLastError());
+    return FBA_OK;
+}
+
+// launch_rel_q, then r and w in PHO order into d_red / d_wst [2 n_pts] (zeroed first: another rank's rows)
+int launch_rel_outputs(Ctx& c, SelInv& si, double* d_q, double* d_red, double* d_wst) {
+    int rc;
+    FBA_HIP(hipMemsetAsync(d_red, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
+    FBA_HIP(hipMemsetAsync(d_wst, 0, sizeof(double) * 2 * std::max<int64_t>(c.n_pts, 1), c.stream));
+    if (c.n_obs == 0) return FBA_OK;
+    if ((rc = launch_rel_q(c, si, d_q))) return rc;
     k_rel_finish<<<(unsigned)((c.n_obs + 255) / 256), 256, 0, c.stream>>>(d_q, c.d_res, c.d_obs_pho, c.n_obs,
                                                                          c.set.meas_std_x, c.set.meas_std_y,
                                                                          c.whiten_on() ? c.d_seff : nullptr, d_red, d_wst);

@@ -521,6 +521,56 @@ def read_rsc(path):
     return names, np.array(used, dtype=np.int64), v[:, 0:6], v[:, 6:12], v[:, 12:15], words
 
 
+VCE_STATUS = ("OK", "EMPTY", "WEAK", "CLIPPED")  # FBA_VCE_*
+
+
+def write_vce(path, res):
+    """The variance-component table <Output_Filename stem>.vce (no reference counterpart: main.m:397-402 fixes the
+    weights), tab-delimited in write_rsd's style, two parts.  Per group, then the rows of no group and the priors
+    (reported only): `G`, name, rows, sum of the redundancy numbers, the component (cumulative variance factor relative
+    to the starting weights), the a-posteriori sigma in pixels (empty for the two report entries), the status word.
+    Per round and group, the history: `R`, round (1-based), name, R, T, n, sigma2.  The G rows' rows and sum r are
+    the last round's."""
+    if getattr(res, "vce_component", None) is None or getattr(res, "vce_table", None) is None:
+        raise ValueError("write_vce: the adjustment carries no variance components (adjust(..., vce=...))")
+    comp = np.asarray(res.vce_component, dtype=np.float64).reshape(-1)
+    sig = np.asarray(res.vce_sigma, dtype=np.float64).reshape(-1)
+    st = np.asarray(res.vce_status).reshape(-1)
+    tab = np.asarray(res.vce_table, dtype=np.float64).reshape(-1, len(comp), 4)
+    names = list(res.vce_names)
+    if not (len(comp) == len(sig) == len(st) == len(names)) or len(tab) < 1:
+        raise ValueError("write_vce: one name, component, sigma and status per group and at least one round expected")
+    with open(path, "w") as fh:
+        for g, name in enumerate(names):
+            fh.write("\t".join(["G", name, str(int(tab[-1, g, 2])), _cell(tab[-1, g, 0]), _cell(comp[g]),
+                                "" if math.isnan(sig[g]) else _cell(sig[g]), VCE_STATUS[int(st[g])]]) + "\n")
+        for k in range(len(tab)):
+            for g, name in enumerate(names):
+                fh.write("\t".join(["R", str(k + 1), name] + [_cell(x) for x in tab[k, g]]) + "\n")
+
+
+def read_vce(path):
+    """write_vce's table back: (names, rows (g), sum r (g), component (g), sigma (g) -- NaN for an empty cell --,
+    status words (g), table (rounds, g, 4))"""
+    names, head, words, hist = [], [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if c[0] == "G" and len(c) == 7:
+                names.append(c[1])
+                head.append([float(c[2]), float(c[3]), float(c[4]), float(c[5]) if c[5] else math.nan])
+                words.append(c[6])
+            elif c[0] == "R" and len(c) == 7:
+                hist.append([float(x) for x in c[3:7]])
+            else:
+                raise ValueError(f"read_vce: {path}: expected 7 tab-separated columns starting with G or R")
+    h = np.array(head, dtype=np.float64).reshape(-1, 4)
+    if not names or len(hist) % len(names):
+        raise ValueError(f"read_vce: {path}: the history does not hold whole rounds")
+    return (names, h[:, 0].astype(np.int64), h[:, 1], h[:, 2], h[:, 3], words,
+            np.array(hist, dtype=np.float64).reshape(-1, len(names), 4))
+
+
 def read_prr(path):
     """write_prr's table back: (names, values (n, 6): prior, std, adjusted, v, r, w -- NaN for an empty cell --,
     flagged (n) bool)"""

@@ -512,6 +512,63 @@ int fba_resect_host(int32_t type, int64_t n, const double* xyz /*[3n]*/,
                     const int32_t* ray_status /*[n] or NULL*/, double c, double ydir, double std_x, double std_y,
                     const fba_resect_options* o, double* eop /*[6]*/, double* quality /*[5]*/, int32_t* status);
 
+/* Variance component estimation over groups of image measurements (no reference counterpart: main.m:397-402 gives
+ * every measurement the weight 1 / Meas_std^2 and everything after the loop inherits it).  Foerstner's simplified
+ * estimator for a diagonal weight matrix (csrc/fba_vce.h).  The 2 n_pts observation rows (PHO order, x y interleaved
+ * like v) carry a group id in [0, n_groups), or -1: the row belongs to no estimated group and keeps its weight.
+ * One round:
+ *   1  Gauss-Newton steps from the device xhat while deltasum > Threshold_Value, at least one, at most Iteration_Cap;
+ *   2  the selected inverse and q = a Cx a' per row, as the reliability function forms it;
+ *   3  per row r = 1 - q / sigma^2 and t = (s v / sigma)^2, s the current sqrt weight (1 without weights), sigma
+ *      Meas_std (Meas_std_y for a y row); per group R = sum r, T = sum t, n the row count; sigma2 = T / R;
+ *   4  status per group: EMPTY n = 0; WEAK R < min_redundancy (factor 1, weights kept); CLIPPED the estimate lies
+ *      outside [1 / clip, clip] and is clamped to it (T = 0 gives 1 / clip); OK otherwise.  Converged: every OK group
+ *      has |sigma2 - 1| <= tol and no group is CLIPPED;
+ *   5  not converged and not the last allowed round: the sqrt weights of each group's rows are multiplied in place by
+ *      1 / sqrt(sigma2) and component[g] *= sigma2 -- the group's cumulative variance factor relative to its
+ *      starting weights (user weights are allowed: they are the starting weights).
+ * After the last round one further plain Gauss-Newton step leaves the context as the adjustment loop leaves one that
+ * was given these weights: the residuals, the post-fit outputs and the weight getter work unchanged, and the getter
+ * returns starting weight / component[group].
+ * Two further entries close the redundancy sum (sum of R over all n_groups + 2 = n + n_prior - u, + 7 with inner
+ * constraints); they are reported and never rescaled (component 1): [n_groups] the rows with id -1, [n_groups + 1]
+ * the context's priors, R = sum (1 - p_j Cx_jj), T = sum p_j v_j^2, host arithmetic on the cofactor diagonal.  The
+ * priors' sigma stay constants of the context: the image groups are estimated RELATIVE TO the stated prior accuracies.
+ *   component [n_groups + 2]; table [max_rounds][n_groups + 2][4]: R, T, n and the sigma2 the round found (1 for EMPTY
+ *   and WEAK, the clamped value for CLIPPED; T / R for the two report entries), rows of rounds not run are left alone;
+ *   status [n_groups + 2] of the last round (the report entries: OK, or EMPTY without rows); *rounds the rounds run;
+ *   *iterations every Gauss-Newton step of the call, the final one included; *converged 1 / 0.  Any output pointer
+ *   may be NULL.  max_rounds exhausted is FBA_OK with *converged = 0; max_rounds = 1 estimates only and leaves the
+ *   weighting untouched.  A non-finite sum returns FBA_ERR_NONFINITE.
+ * Checked on the host before any GPU call, FBA_ERR_ARG: n_groups outside [1, FBA_VCE_MAX_GROUPS], an id outside
+ * [-1, n_groups), a non-finite or out-of-range option (max_rounds >= 1, tol >= 0, min_redundancy >= 0, clip >= 1), a
+ * call between the asynchronous solve and its finish.  FBA_ERR_UNSUPPORTED: world > 1; a robust loss (its IRLS factor
+ * and a variance component would fight over the same residuals); damping > 0.  A refused call leaves the context
+ * untouched.  The first rescale of an unweighted context switches its weights on (the accumulation graph is
+ * re-captured once, as by the weight setter); later rescales write in place and re-capture nothing.  One GPU, plain
+ * launches on the context's stream, fixed-order sums: two calls on two fresh contexts are bitwise equal.  With
+ * fba_set_timing on, fba_last_timings' [7] afterwards holds the device time of the call's own kernels (the
+ * reliability part and the group sums of every round, not the steps), [0..6] 0.
+ * fba_vce_host (host only, no GPU): the group sums in index order over n_rows rows with given r and t, then the same
+ *   estimate, clamp, factor and status: sums [n_groups + 1][3] R T n (row n_groups: id -1), sigma2 / factor / status
+ *   [n_groups].  Non-finite sums: the outputs are filled and FBA_ERR_NONFINITE is returned. */
+enum { FBA_VCE_OK = 0, FBA_VCE_EMPTY = 1, FBA_VCE_WEAK = 2, FBA_VCE_CLIPPED = 3 };
+#define FBA_VCE_MAX_GROUPS 256
+typedef struct fba_vce_options {
+    int32_t max_rounds;      /* >= 1; default (NULL options) 10; 1 = estimate only, nothing re-weighted */
+    int32_t reserved;
+    double  tol;             /* default 1e-3 */
+    double  min_redundancy;  /* default 1.0  */
+    double  clip;            /* default 100  */
+} fba_vce_options;
+int fba_vce(fba_ctx* ctx, int32_t n_groups, const int32_t* group /*[2 n_pts] PHO order, x y interleaved*/,
+            const fba_vce_options* o, double* component /*[n_groups+2]*/,
+            double* table /*[max_rounds][n_groups+2][4]: R, T, n, sigma2 of the round*/,
+            int32_t* status /*[n_groups+2], last round*/, int32_t* rounds, int32_t* iterations, int32_t* converged);
+int fba_vce_host(int64_t n_rows, int32_t n_groups, const int32_t* group, const double* r, const double* t,
+                 const fba_vce_options* o, double* sums /*[n_groups+1][3]*/, double* sigma2, double* factor,
+                 int32_t* status);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
