@@ -15,6 +15,10 @@
                                                default), per camera or per camera and axis, estimated and applied
                                                on the device before the post-fit outputs; also writes the .vce table
                                                (report.write_vce); not together with --robust
+    ... main <folder> ... --snoop[=crit]       Baarda data snooping: the image points whose w-test exceeds crit (3.29)
+                                               are eliminated on the device round by round and re-checked at the end;
+                                               also writes the .snp table (report.write_snp); --reliability then shows
+                                               the cleaned block; not together with --robust
     python fba_cli.py batch <folder>...        BatchRun.m without its folder picker
     ... --robust huber[:k] | cauchy[:k]        (either command) robust loss after the L2 iterations, k in units
                                                of sigma (default: the 95 %-efficiency constants, huber 1.345,

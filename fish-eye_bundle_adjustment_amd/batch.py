@@ -151,6 +151,26 @@ def parse_vce(args):
     return rest, vce
 
 
+def parse_snoop(args):
+    """--snoop or --snoop=<crit> anywhere in args -> (args without it, None, True or the critical value): Baarda data
+    snooping of the image points (`main` only; writes the .snp table).  ValueError for a crit that is not a positive
+    number."""
+    rest, snoop = [], None
+    for a in args:
+        if a == "--snoop":
+            snoop = True
+        elif a.startswith("--snoop="):
+            try:
+                snoop = float(a.split("=", 1)[1])
+            except ValueError:
+                snoop = float("nan")
+            if not (snoop > 0.0 and snoop < float("inf")):
+                raise ValueError("--snoop: the critical value must be a positive number")
+        else:
+            rest.append(a)
+    return rest, snoop
+
+
 def parse_robust(args):
     """--robust huber[:k] | cauchy[:k] (also --robust=...) anywhere in args -> (args without it, loss or None,
     k or None).  ValueError for a missing or unknown loss, or a k that is not a positive number."""
@@ -182,13 +202,13 @@ def parse_robust(args):
 def parse_main(args):
     """`main`'s arguments <folder> [plot] [--reliability] -> (folder, plot, reliability); the flag may stand
     anywhere after the folder (a --robust option is parse_robust's, --priors parse_priors', --lm parse_lm's)"""
-    args = parse_vce(parse_resect(args)[0])[0]
+    args = parse_snoop(parse_vce(parse_resect(args)[0])[0])[0]
     args = parse_intersect(parse_ellipsoids(parse_lm(parse_priors(parse_robust(args)[0])[0])[0])[0])[0]
     rest = [a for a in args[1:] if a != "--reliability"]
     return args[0], bool(rest) and rest[0] not in ("0", "false"), "--reliability" in args[1:]
 
 
-USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--resect[=control|all]] [--vce[=xy|camera|camera_xy]] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
+USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] [--intersect] [--resect[=control|all]] [--vce[=xy|camera|camera_xy]] [--snoop[=crit]] [--robust LOSS[:k]] [--priors] [--lm[=lambda0]] | "
          "batch <folder>... [--robust LOSS[:k]] [--priors] [--lm[=lambda0]]\n  --robust huber[:k] | cauchy[:k]  robust loss after the L2 iterations, "
          "re-weighted at every linearisation;\n      k in units of sigma, default the 95 %-efficiency constant: huber "
          "1.345, cauchy 2.385; writes the .wgt table\n  --priors  the folder's .pri table (<unknown name> <value> "
@@ -201,7 +221,8 @@ USAGE = ("usage: fba_cli.py main <folder> [plot] [--reliability] [--ellipsoids] 
          "points (all: and\n      the tie points at their .cnt coordinates) instead of the .ext values; writes the .rsc "
          "table\n  --vce[=xy|camera|camera_xy]  (main) variance components of the image measurements per axis, per camera or "
          "per camera and\n      axis, estimated and applied before the post-fit outputs (not with --robust); writes the "
-         ".vce table")
+         ".vce table\n  --snoop[=crit]  (main) Baarda data snooping: image points whose w-test exceeds crit (3.29) are "
+         "eliminated on the\n      device round by round and re-checked at the end (not with --robust); writes the .snp table")
 
 
 def cli(argv=None):
@@ -218,6 +239,9 @@ def cli(argv=None):
         argv, vce = parse_vce(argv)
         if vce and robust:
             raise ValueError("--vce cannot be combined with --robust")
+        argv, snoop = parse_snoop(argv)
+        if snoop and robust:
+            raise ValueError("--snoop cannot be combined with --robust")
     except ValueError as e:
         print(f"Error: {e}")
         print(USAGE)
@@ -228,7 +252,7 @@ def cli(argv=None):
         return main(folder, plot, reliability=reliability, **_robust_kw(robust, robust_k), **_priors_kw(priors),
                     **_lm_kw(lm), **({"ellipsoids": True} if ellipsoids else {}),
                     **({"intersect": True} if intersect else {}), **({"resect": resect} if resect else {}),
-                    **({"vce": vce} if vce else {}))
+                    **({"vce": vce} if vce else {}), **({"snoop": snoop} if snoop else {}))
     if len(argv) >= 2 and argv[0] == "batch":
         done = batch_run(argv[1:], **_robust_kw(robust, robust_k), **_priors_kw(priors), **({"lm": lm} if lm else {}))
         return 1 if any(e for _, e in done) else 0

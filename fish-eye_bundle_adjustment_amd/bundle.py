@@ -119,6 +119,16 @@ class Adjustment:
     vce_rounds: int = None
     vce_names: list = None
     vce_converged: bool = None
+    # data snooping (snoop=...), PHO order: per image point 0 active / 1 excluded / 2 re-admitted (capi.SNOOP_STATE),
+    # W (or W~ of an excluded point) of the last round, the per-round table [picked, passed by the back-check,
+    # excluded after the round, largest active W], and sigma0^2 over the active rows alone:
+    # v'Pv / (n - 2 n_excluded + n_prior - u, + 7 with inner constraints)
+    snoop_excluded: np.ndarray = None  # (n_pts) uint8
+    snoop_stat: np.ndarray = None      # (n_pts)
+    snoop_table: np.ndarray = None     # (rounds, 4)
+    snoop_rounds: int = None
+    snoop_converged: bool = None
+    sigma02_active: float = None
 
 
 def _priors_of(data, priors):
@@ -174,7 +184,7 @@ def vce_groups(packed, vce):
 
 def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, verbose=False, covariance=True,
            reliability=False, priors=None, method="gn", lm_options=None, point_precision=False,
-           intersect=False, resect=False, vce=None, vce_options=None) -> Adjustment:
+           intersect=False, resect=False, vce=None, vce_options=None, snoop=None) -> Adjustment:
     """main.m:386-602 on one GPU: Buildxhat, the Gauss-Newton loop, residuals, sigma0^2 and (with
     covariance=True) the post-fit Cx diagonal and correlation sub-blocks (main.m:428-482, :602).
     reliability=True calls fba_reliability instead of fba_covariance: the same two outputs plus the
@@ -223,9 +233,24 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
     after the damped loop, otherwise in place of the plain loop.  sigma0^2, Cx, the reliability numbers and the
     ellipsoids then come from the re-weighted last pass, Adjustment.weights holds the weights and Adjustment.vce_*
     the components.  Priors keep their stated accuracy: the groups are estimated relative to it.  Together with
-    robust= it raises ValueError (the loss factor and a variance component would fight over the same residuals)."""
+    robust= it raises ValueError (the loss factor and a variance component would fight over the same residuals).
+
+    snoop (no reference counterpart: main.m never tests a measurement): True, a critical value, or a dict of
+    capi.Context.snoop's options -- Baarda data snooping on the device (fba_snoop): the image points whose w-test
+    exceeds crit are eliminated round by round (weight 1e-12 x theirs) and re-checked once the adjustment is clean.
+    It runs after resect / intersect; with method="lm" after the damped loop, otherwise in place of the plain loop;
+    before vce, where the excluded rows join no group (id -1).  The call consumes the last factor, so one further
+    step precedes the post-fit outputs.  sigma0^2, Cx and the reliability numbers are those of the cleaned last pass;
+    Adjustment.snoop_* carry the states, statistics and rounds, Adjustment.sigma02_active the variance factor over the
+    active rows alone (sigma02 still counts every row).  Together with robust= it raises ValueError."""
     if vce is not None and robust:
         raise ValueError("adjust: vce together with robust is not supported")
+    if snoop is False:
+        snoop = None
+    if snoop is not None and robust:
+        raise ValueError("adjust: snoop together with robust is not supported")
+    if snoop is not None:
+        snoop = {} if snoop is True else dict(snoop) if isinstance(snoop, dict) else {"crit": float(snoop)}
     if resect not in (False, None, True, "control", "all"):
         raise ValueError(f"adjust: unknown resect {resect!r} (True, \"control\" or \"all\")")
     if method not in ("gn", "lm"):
@@ -247,13 +272,24 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         if method == "lm":
             nt, npol, lmh = ctx.adjust_lm(lm_options)
             it, hist = nt + npol, lmh[:, 2].copy()
-        elif vce is None:
+        elif vce is None and snoop is None:
             it, hist = ctx.adjust()
         else:
             it, hist = 0, np.zeros(0)
+        skw = {}
+        if snoop is not None:
+            sn = ctx.snoop(**snoop)
+            it += sn["iterations"]
+            skw = dict(snoop_excluded=sn["excluded"], snoop_stat=sn["stat"], snoop_table=sn["table"],
+                       snoop_rounds=sn["rounds"], snoop_converged=sn["converged"])
+            if vce is None and (covariance or reliability or point_precision):
+                ctx.step()  # fba_snoop consumed the factor of its last solve
+                it += 1
         vkw = {}
         if vce is not None:
             grp, names = vce_groups(ctx.packed, vce)
+            if snoop is not None:
+                grp = np.where(np.repeat(skw["snoop_excluded"] == 1, 2), -1, grp).astype(np.int32)
             vr = ctx.vce(grp, len(names), **(vce_options or {}))
             it += vr["iterations"]
             std = np.full(len(names) + 2, np.nan)
@@ -275,7 +311,11 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         t1 = time.perf_counter()
         xhat = ctx.get_xhat()
         v, rsd, st = ctx.residuals()
-        eff = ctx.get_weights() if (weights is not None or robust or vce is not None) else None
+        eff = ctx.get_weights() if (weights is not None or robust or vce is not None or snoop is not None) else None
+        if snoop is not None:
+            n_ex = int(np.count_nonzero(skw["snoop_excluded"] == 1))
+            dof = st[5] - 2 * n_ex + (7 if int(data.settings.get("Inner_Constraints", 0)) else 0)
+            skw["sigma02_active"] = float(st[4] / dof) if dof > 0 else float("nan")
         red = wst = None
         ppk = {}
         if point_precision:
@@ -295,7 +335,7 @@ def adjust(data: Dataset, weights=None, robust=None, robust_k=None, device=0, ve
         ctx.close()
     return Adjustment(xhat=xhat, xhatnames=xhat_names(data), iterations=it, deltasum=hist, v=v, rsd=rsd,
                       rms=(st[0], st[1], st[2]), sigma02=st[3], seconds=t1 - t0, cx_diag=cxd, corr=corr,
-                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk, **ikw, **vkw)
+                      redundancy=red, wstat=wst, weights=eff, lm_history=lmh, **pkw, **ppk, **ikw, **vkw, **skw)
 
 
 def write_outputs(data: Dataset, res: Adjustment, folder):
@@ -323,11 +363,14 @@ def write_outputs(data: Dataset, res: Adjustment, folder):
         report.write_rsc(os.path.join(folder, name + ".rsc"), data, res)
     if getattr(res, "vce_component", None) is not None:
         report.write_vce(os.path.join(folder, name + ".vce"), res)
+    if getattr(res, "snoop_excluded", None) is not None:
+        report.write_snp(os.path.join(folder, name + ".snp"), data, res)
     return out
 
 
 def main(folder: str = "", plot: bool = False, device=0, reliability=False, robust=None, robust_k=None,
-         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False, resect=False, vce=None) -> int:
+         priors=False, method="gn", lm_options=None, ellipsoids=False, intersect=False, resect=False, vce=None,
+         snoop=None) -> int:
     """main.m:10 contract: returns main_error (0 ok, 1 failure).  Plots (main.m:502-584) are not
     produced; `plot` is accepted for signature compatibility.  reliability=True also writes the .rel
     table (report.write_rel) beside the .out / .par / .rsd files, which stay as without it.  robust / robust_k:
@@ -340,7 +383,8 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
     (report.write_fwd) is written too.  resect=True / "control" / "all": adjust()'s resect -- the images' starting
     values by space resection instead of the .ext file; the .rsc table (report.write_rsc) is written too.
     vce="xy" / "camera" / "camera_xy": adjust()'s vce -- variance components of the image measurements' groups; the
-    .vce table (report.write_vce) is written too."""
+    .vce table (report.write_vce) is written too.  snoop=True / a critical value: adjust()'s snoop -- Baarda data
+    snooping of the image points; the .snp table (report.write_snp) is written too."""
     project_dir = os.getcwd()
     folder = folder or project_dir
     try:
@@ -351,6 +395,7 @@ def main(folder: str = "", plot: bool = False, device=0, reliability=False, robu
                      **({"intersect": True} if intersect else {}),
                      **({"resect": resect} if resect else {}),
                      **({"vce": vce} if vce else {}),
+                     **({"snoop": snoop} if snoop else {}),
                      **({"method": method, "lm_options": lm_options} if method != "gn" else {}))
         write_outputs(data, res, folder)
     except (IngestError, capi.FBAError) as e:

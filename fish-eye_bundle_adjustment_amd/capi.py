@@ -24,6 +24,7 @@ ISECT_STATUS = ("ok", "few", "weak", "refine")   # FBA_ISECT_*
 RESECT_STATUS = ("ok", "few", "weak", "refine")  # FBA_RESECT_*
 RESECT_USE = ("control", "all")                  # FBA_RESECT_USE_*
 VCE_STATUS = ("ok", "empty", "weak", "clipped")  # FBA_VCE_*
+SNOOP_STATE = ("active", "excluded", "readmitted")  # fba_snoop's excluded[] on exit
 VCE_MAX_GROUPS = 256                             # FBA_VCE_MAX_GROUPS
 
 # every symbol include/fba.h declares
@@ -40,6 +41,7 @@ EXPORTS = (
     "fba_unproject_host", "fba_image_rays", "fba_intersect",
     "fba_resect", "fba_resect_host",
     "fba_vce", "fba_vce_host",
+    "fba_snoop", "fba_snoop_host",
 )
 # ... but for the host-only helpers whose names carry a digit (tests/test_damping_host.py reads the header's
 # declarations with a letters-only pattern and compares them with EXPORTS)
@@ -121,6 +123,15 @@ class VceOptions(C.Structure):
         super().__init__(int(max_rounds), 0, float(tol), float(min_redundancy), float(clip))
 
 
+class SnoopOptions(C.Structure):
+    """fba_snoop_options; the defaults are the library's (a NULL pointer)"""
+    _fields_ = [("max_rounds", C.c_int32), ("min_rays", C.c_int32), ("min_img_points", C.c_int32), ("reserved", C.c_int32),
+                ("crit", C.c_double), ("max_share", C.c_double)]
+
+    def __init__(self, max_rounds=20, min_rays=2, min_img_points=6, crit=3.29, max_share=0.05):
+        super().__init__(int(max_rounds), int(min_rays), int(min_img_points), 0, float(crit), float(max_share))
+
+
 def pack_priors(priors):
     """(index, value, sigma) -> (fba_priors, the arrays it points into), or (None, None) for None / no rows.
     Shapes only: the values are checked by fba_create_priors, on the host, before it touches the GPU."""
@@ -194,6 +205,8 @@ def _load():
         "fba_resect_host": ([I, C.c_int64, P, P, P, D, D, D, D, P, P, P, P], C.c_int),
         "fba_vce": ([P, I, P, P, P, P, P, P, P, P], C.c_int),
         "fba_vce_host": ([C.c_int64, I, P, P, P, P, P, P, P, P], C.c_int),
+        "fba_snoop": ([P, P, P, P, P, P, P, P, P], C.c_int),
+        "fba_snoop_host": ([C.c_int64, P, P, P, P, I, I, P, P, P, P], C.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -555,6 +568,32 @@ class Context:
         return {"component": comp, "table": table[: rounds.value].copy(), "status": st, "rounds": rounds.value,
                 "iterations": its.value, "converged": bool(conv.value)}
 
+    def snoop(self, excluded=None, max_rounds=20, min_rays=2, min_img_points=6, crit=3.29, max_share=0.05):
+        """fba_snoop: Baarda data snooping over the image points on the device -- rounds of adjustment, w-test,
+        elimination of the local maxima above crit (at most one per tie point and per image in a round) and, once a
+        round eliminates nothing, re-admission of the excluded points whose predicted residual passes the test.
+        excluded: (n_pts) nonzero = the point starts excluded (PHO order), or None.  Returns a dict: excluded (n_pts)
+        uint8 0 active / 1 excluded / 2 re-admitted (capi.SNOOP_STATE); stat (n_pts) W or W~ of the last round; table
+        (rounds, 4): picked, passed by the back-check, excluded after the round, largest active W; rounds, iterations,
+        converged, status_bits (bit 1: the max_share stop).  Afterwards xhat, residuals() and get_weights() are those
+        of adjust() with the final weights (1e-12 x the starting weight on the excluded points); the call consumed
+        the last factor, so postfit() needs one step() first.  One GPU, no robust loss, no damping."""
+        n = self.packed.n_pts
+        ex = np.zeros(max(n, 1), dtype=np.uint8)
+        if excluded is not None:
+            e = np.asarray(excluded).reshape(-1)
+            if e.size != n:
+                raise ValueError("snoop: excluded must have n_pts entries")
+            ex[:n] = e != 0
+        op = SnoopOptions(max_rounds, min_rays, min_img_points, crit, max_share)
+        stat = np.zeros(max(n, 1))
+        table = np.zeros((max(int(max_rounds), 1), 4))
+        rounds, its, conv, bits = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(lib.fba_snoop(self.h, C.byref(op), ptr(ex), ptr(stat), ptr(table), C.byref(rounds), C.byref(its),
+                            C.byref(conv), C.byref(bits)))
+        return {"excluded": ex[:n], "stat": stat[:n], "table": table[: rounds.value].copy(), "rounds": rounds.value,
+                "iterations": its.value, "converged": bool(conv.value), "status_bits": bits.value}
+
     def set_spin_bound(self, spins=0):
         """(tests) this context's hand-off poll bound in sleeps; 0 restores the default"""
         check(lib.fba_set_spin_bound(self.h, int(spins)))
@@ -645,6 +684,28 @@ def vce_host(group, r, t, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0,
     check(lib.fba_vce_host(n, int(n_groups), ptr(g) if n else None, ptr(r) if n else None, ptr(t) if n else None,
                            C.byref(op), ptr(sums), ptr(s2), ptr(f), ptr(st)))
     return sums, s2[:ng], f[:ng], st[:ng]
+
+
+def snoop_host(W, state, tie, img, n_tie=None, n_img=None, max_rounds=20, min_rays=2, min_img_points=6, crit=3.29,
+               max_share=0.05):
+    """fba_snoop_host: one round's selection of the data snooping (csrc/fba_snoop.h) run on the CPU in index order, no
+    GPU needed.  W (n) the points' statistics, state (n) 0 active / 1 excluded / 2 re-admitted, tie (n) the tie point
+    (< 0: a control observation), img (n) the image -> (pick, readmit (n) bool, status_bits)."""
+    W = np.ascontiguousarray(W, dtype=np.float64).reshape(-1)
+    state = np.ascontiguousarray(state, dtype=np.uint8).reshape(-1)
+    tie = np.ascontiguousarray(tie, dtype=np.int32).reshape(-1)
+    img = np.ascontiguousarray(img, dtype=np.int32).reshape(-1)
+    n = W.size
+    if not (state.size == tie.size == img.size == n):
+        raise ValueError("snoop_host: W, state, tie and img must have the same length")
+    n_tie = int(tie.max(initial=-1)) + 1 if n_tie is None else int(n_tie)
+    n_img = int(img.max(initial=-1)) + 1 if n_img is None else int(n_img)
+    op = SnoopOptions(max_rounds, min_rays, min_img_points, crit, max_share)
+    pick, back = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    bits = C.c_int32()
+    z = lambda a: ptr(a) if n else None
+    check(lib.fba_snoop_host(n, z(W), z(state), z(tie), z(img), n_tie, n_img, C.byref(op), z(pick), z(back), C.byref(bits)))
+    return pick[:n].astype(bool), back[:n].astype(bool), bits.value
 
 
 def tie_blocks(cx_tie):

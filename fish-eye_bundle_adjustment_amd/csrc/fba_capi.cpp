@@ -25,6 +25,7 @@
 #include "fba_ray.h"
 #include "fba_resect.h"
 #include "fba_vce.h"
+#include "fba_snoop.h"
 
 namespace fba {
 
@@ -1647,6 +1648,191 @@ int fba_vce_host(int64_t n_rows, int32_t n_groups, const int32_t* group, const d
         if (status) status[g] = st;
     }
     if (!finite) { set_error("fba_vce_host: a non-finite group sum"); return FBA_ERR_NONFINITE; }
+    return FBA_OK;
+}
+
+// ---- Baarda data snooping over the image points (no reference counterpart) ----
+namespace fba {
+static const fba_snoop_options kSnoopDefaults{20, 2, 6, 0, 3.29, 0.05};
+static int check_snoop_options(const char* who, const fba_snoop_options& op) {
+    if (op.max_rounds < 1 || op.min_rays < 1 || op.min_img_points < 1 || !std::isfinite(op.crit) || !(op.crit > 0.0) ||
+        !std::isfinite(op.max_share) || !(op.max_share > 0.0) || op.max_share > 1.0) {
+        set_error(std::string(who) + ": max_rounds, min_rays and min_img_points >= 1; crit > 0 and 0 < max_share <= 1, both finite");
+        return FBA_ERR_ARG;
+    }
+    return FBA_OK;
+}
+// the point list on first use: d_pt downloaded once, sorted on the host (build_point_list), kept by the context
+static int point_list_once(Ctx* c) {
+    if (c->have_pt_list) return FBA_OK;
+    std::vector<int32_t> pt((size_t)c->n_obs), start, list;
+    if (c->n_obs > 0) FBA_HIP(hipMemcpy(pt.data(), c->d_pt, sizeof(int32_t) * pt.size(), hipMemcpyDeviceToHost));
+    const int64_t n_pl = c->n_lp + c->gen.n_gp;  // d_pt counts the general points after the regular ones
+    for (int32_t p : pt)
+        if (p >= n_pl) { set_error("fba_snoop: an observation's local point is out of range"); return FBA_ERR_ARG; }
+    build_point_list(pt, (int)n_pl, start, list);
+    int rc;
+    if ((rc = upload(*c, &c->d_pl_start, start)) || (rc = upload(*c, &c->d_pl_obs, list))) return rc;
+    c->n_pl = n_pl;
+    c->have_pt_list = true;
+    return FBA_OK;
+}
+}  // namespace fba
+
+int fba_snoop(fba_ctx* ctx, const fba_snoop_options* o, uint8_t* excluded, double* stat, double* table, int32_t* rounds,
+              int32_t* iterations, int32_t* converged, int32_t* status_bits) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("fba_snoop: NULL context"); return FBA_ERR_ARG; }
+    if (c->pending) { set_error("fba_snoop between fba_solve_update_async and fba_solve_finish"); return FBA_ERR_ARG; }
+    const fba_snoop_options& op = o ? *o : kSnoopDefaults;
+    int rc;
+    if ((rc = check_snoop_options("fba_snoop", op))) return rc;
+    if (c->opt.world != 1) { set_error("fba_snoop is single-GPU (world == 1)"); return FBA_ERR_UNSUPPORTED; }
+    if (c->loss != FBA_LOSS_NONE) {
+        set_error("fba_snoop with a robust loss set: the w-test wants the residuals of a plain L2 adjustment");
+        return FBA_ERR_UNSUPPORTED;
+    }
+    if (c->damp_on()) { set_error("fba_snoop with damping > 0: the factor of a damped solve is not that of N"); return FBA_ERR_UNSUPPORTED; }
+    if ((int)c->img_ord.size() != c->L.n_img) { set_error("fba_snoop: image order and layout disagree"); return FBA_ERR_ARG; }
+    if ((rc = image_list_once(c)) || (rc = point_list_once(c))) return rc;
+
+    const int64_t n = c->n_obs;
+    const size_t no = (size_t)std::max<int64_t>(n, 1), nseg = (size_t)std::max<int64_t>(c->n_pl + c->L.n_img, 1);
+    const int64_t n_blocks = (n + 255) / 256;
+    SnoopBufs b;
+    double* d_q = nullptr;
+    if ((rc = ws_get(*c, WS_SNOOP_S0, 2 * no, &b.s0)) || (rc = ws_get(*c, WS_SNOOP_W, no, &b.W)) ||
+        (rc = ws_get(*c, WS_SNOOP_STATE, no, &b.state)) || (rc = ws_get(*c, WS_SNOOP_CAND, no, &b.cand)) ||
+        (rc = ws_get(*c, WS_SNOOP_BACK, no, &b.back)) || (rc = ws_get(*c, WS_SNOOP_WIN, nseg, &b.win)) ||
+        (rc = ws_get(*c, WS_SNOOP_CNT, nseg, &b.cnt)) || (rc = ws_get(*c, WS_SNOOP_PICK, (size_t)std::max(c->L.n_img, 1), &b.pick)) ||
+        (rc = ws_get(*c, WS_SNOOP_PART, (size_t)std::max<int64_t>(n_blocks, 1) * SNOOP_PART, &b.part)) ||
+        (rc = ws_get(*c, WS_SNOOP_OUT, (size_t)SNOOP_OUT, &b.out)) || (rc = ws_get(*c, WS_REL_Q, 2 * no, &d_q)))
+        return rc;
+    // the starting state in local order
+    std::vector<uint8_t> st(no, SNOOP_ACTIVE);
+    int64_t n_excl = 0;
+    if (excluded)
+        for (int64_t i = 0; i < n; ++i) {
+            st[(size_t)i] = excluded[c->obs_pho[i]] ? SNOOP_EXCLUDED : SNOOP_ACTIVE;
+            n_excl += st[(size_t)i] == SNOOP_EXCLUDED;
+        }
+    FBA_HIP(hipMemcpyAsync(b.state, st.data(), st.size(), hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_snoop_init(*c, b))) return rc;
+    FBA_HIP(hipStreamSynchronize(c->stream));  // (st is pageable memory of this call)
+    // a change of the weights: the first one of an unweighted context switches the weighted kernels on
+    auto apply = [&](int mode) -> int {
+        int r;
+        if (!c->weights_on && ((r = weight_buffers(c)) || (r = weighting_changed(c)))) return r;
+        if ((r = launch_snoop_apply(*c, b, mode))) return r;
+        FBA_HIP(hipStreamSynchronize(c->stream));
+        c->weights_on = true;
+        c->have_lin = false;  // neither the linearisation nor the factor belongs to the new weights
+        c->have_factor = false;
+        return FBA_OK;
+    };
+    if (n_excl > 0 && (rc = apply(0))) return rc;
+
+    hipEvent_t e0 = nullptr, e1 = nullptr;  // events of the call's own: the steps in between use the context's
+    if (c->timing) {
+        FBA_HIP(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); set_error("fba_snoop: hipEventCreate failed"); return FBA_ERR_HIP; }
+    }
+    struct EvGuard {
+        hipEvent_t a, b;
+        ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    } guard{e0, e1};
+
+    int n_rounds = 0, n_iter = 0, conv = 0, bits = 0;
+    double own_ms = 0.0;
+    auto publish = [&]() -> int {
+        if (rounds) *rounds = n_rounds;
+        if (iterations) *iterations = n_iter;
+        if (converged) *converged = conv;
+        if (status_bits) *status_bits = bits;
+        if (c->timing) {
+            std::fill(c->last_ms, c->last_ms + 8, 0.0);
+            c->last_ms[7] = own_ms;
+        }
+        if (n > 0 && (excluded || stat)) {
+            std::vector<double> w((size_t)n, 0.0);
+            if (n_rounds > 0) FBA_HIP(hipMemcpyAsync(w.data(), b.W, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+            FBA_HIP(hipMemcpyAsync(st.data(), b.state, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+            FBA_HIP(hipStreamSynchronize(c->stream));
+            for (int64_t i = 0; i < n; ++i) {
+                if (excluded) excluded[c->obs_pho[i]] = st[(size_t)i];
+                if (stat) stat[c->obs_pho[i]] = w[(size_t)i];
+            }
+        }
+        return FBA_OK;
+    };
+    double out[SNOOP_OUT] = {0, 0, 0, 0};
+    for (int k = 0; k < op.max_rounds; ++k) {
+        int32_t it = 0;
+        rc = fba_adjust(ctx, &it, nullptr);
+        n_iter += it;
+        if (rc) { (void)publish(); return rc; }
+        if (!c->have_factor || !c->have_delta) { (void)publish(); set_error("fba_snoop: the last solve left no factor"); return FBA_ERR_ARG; }
+        if (c->timing) (void)hipEventRecord(e0, c->stream);
+        if ((rc = launch_vce_q(*c, nullptr, nullptr, d_q)) ||
+            (rc = launch_snoop_round(*c, b, d_q, op.min_rays, op.min_img_points, op.crit))) {
+            (void)publish();
+            return rc;
+        }
+        if (c->timing) (void)hipEventRecord(e1, c->stream);
+        FBA_HIP(hipMemcpyAsync(out, b.out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+        FBA_HIP(hipStreamSynchronize(c->stream));
+        if (c->timing) {
+            float ms = 0.f;
+            FBA_HIP(hipEventElapsedTime(&ms, e0, e1));
+            own_ms += ms;
+        }
+        n_rounds = k + 1;
+        const int64_t n_pick = (int64_t)out[0], n_back = n_pick ? 0 : (int64_t)out[1];
+        n_excl = (int64_t)out[2];
+        const bool last = k == op.max_rounds - 1;
+        const bool stop = n_pick > 0 && snoop_share_stop(n_excl, n_pick, c->n_pts, op.max_share);
+        const bool change = (n_pick > 0 || n_back > 0) && !last && !stop;
+        if (table) {
+            double* t = table + 4 * (size_t)k;
+            t[0] = (double)n_pick; t[1] = (double)n_back; t[3] = out[3];
+            t[2] = (double)(change ? n_excl + n_pick - n_back : n_excl);
+        }
+        if (n_pick == 0 && n_back == 0) { conv = 1; break; }
+        if (stop) bits |= 2;
+        if (!change) break;
+        if ((rc = apply(n_pick > 0 ? 1 : 2))) { (void)publish(); return rc; }
+    }
+    return publish();
+}
+
+int fba_snoop_host(int64_t n, const double* W, const uint8_t* state, const int32_t* tie, const int32_t* img, int32_t n_tie,
+                   int32_t n_img, const fba_snoop_options* o, uint8_t* pick, uint8_t* readmit, int32_t* status_bits) {
+    const fba_snoop_options& op = o ? *o : kSnoopDefaults;
+    int rc;
+    if ((rc = check_snoop_options("fba_snoop_host", op))) return rc;
+    if (n < 0 || n_tie < 0 || n_img < 0 || (n > 0 && (!W || !state || !tie || !img || !pick || !readmit))) {
+        set_error("fba_snoop_host: n, n_tie, n_img >= 0 and no NULL array");
+        return FBA_ERR_ARG;
+    }
+    int64_t n_excl = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (tie[i] >= n_tie || img[i] < 0 || img[i] >= n_img || state[i] > SNOOP_READMITTED) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "fba_snoop_host: point %ld: tie %d (< %d), img %d (in [0, %d)), state %d (0, 1 or 2)", (long)i,
+                     (int)tie[i], (int)n_tie, (int)img[i], (int)n_img, (int)state[i]);
+            set_error(buf);
+            return FBA_ERR_ARG;
+        }
+        n_excl += state[i] == SNOOP_EXCLUDED;
+    }
+    int64_t n_pick = 0, n_back = 0;
+    snoop_select(n, W, state, tie, img, nullptr, n_tie, n_img, op.min_rays, op.min_img_points, op.crit, pick, readmit, n_pick, n_back);
+    int bits = 0;
+    if (n_pick > 0 && snoop_share_stop(n_excl, n_pick, n, op.max_share)) {
+        bits |= 2;
+        std::fill(pick, pick + n, (uint8_t)0);
+    }
+    if (status_bits) *status_bits = bits;
     return FBA_OK;
 }
 

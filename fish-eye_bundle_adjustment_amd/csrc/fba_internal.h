@@ -204,6 +204,10 @@ enum WsSlot : int {
     WS_RAY, WS_RAY_ST, WS_RAY_XU, WS_ISECT_OUT, WS_ISECT_ST,  // fba_image_rays / fba_intersect
     WS_RESECT_REC, WS_RESECT_USE, WS_RESECT_OUT, WS_RESECT_ST,  // fba_resect: records and flags (list order), outputs
     WS_VCE_GROUP, WS_VCE_SLAB, WS_VCE_OUT,  // fba_vce: group ids (local order), block partial sums, the groups' rows
+    // fba_snoop, local order: the starting sqrt weights, W / W~, the state / candidate / back-check bytes, the segments'
+    // winners and counts, the pick of each image slot, k_snoop_pick's block partials, the round's counts
+    WS_SNOOP_S0, WS_SNOOP_W, WS_SNOOP_STATE, WS_SNOOP_CAND, WS_SNOOP_BACK, WS_SNOOP_WIN, WS_SNOOP_CNT, WS_SNOOP_PICK,
+    WS_SNOOP_PART, WS_SNOOP_OUT,
     WS_COUNT
 };
 static_assert(WS_SEL_END - WS_SEL_Z == 10 && WS_OBS_T >= WS_SEL_END, "launch_selinv's slots run into the next name");
@@ -362,6 +366,12 @@ struct Ctx {
     int32_t* d_il_start = nullptr;   // [n_img+1] list range of each image slot
     int32_t* d_il_obs = nullptr;     // [n_obs] local observations, by image slot
     int32_t* d_il_ext = nullptr;     // [n_img] EXT row of each slot (-1: padding) = img_ord
+    // data snooping (fba_snoop; built on first use): the local observations of each local tie point, ascending; the
+    // points are d_pt's: the n_lp regular ones, then the gen.n_gp general ones
+    bool have_pt_list = false;
+    int64_t n_pl = 0;                // n_lp + gen.n_gp
+    int32_t* d_pl_start = nullptr;   // [n_pl+1] list range of each local tie point
+    int32_t* d_pl_obs = nullptr;     // the tie observations (local indices), by local tie point
     double* h_pinned = nullptr;  // [HPIN_TOTAL] pinned host scratch (coherent, mapped: k_sum_parts mirrors the d_scal
                                  // slots below SCAL_MIRROR here, then HPIN_SEQ = its running count of solves)
     double solve_seq = 0.0;      // solves the host has seen completed (h_pinned[HPIN_SEQ])
@@ -510,6 +520,9 @@ int build_plan(const fba_problem* p, const fba_settings* s, const fba_options& o
 // the observations of each image: start [n_img + 1], list [img.size()] -- a stable counting sort of the observation
 // indices by img[o] (ascending inside an image); entries of img outside [0, n_img) are left out
 void build_image_list(const std::vector<int32_t>& img, int n_img, std::vector<int32_t>& start, std::vector<int32_t>& list);
+// the observations of each local tie point (d_pt's index), the same way: start [n_lp + 1], list; pt < 0 (control) is
+// left out
+void build_point_list(const std::vector<int32_t>& pt, int n_lp, std::vector<int32_t>& start, std::vector<int32_t>& list);
 int64_t count_unknowns(const fba_problem* p, const fba_settings* s);  // the reference's u
 void partition(const fba_problem* p, int world, std::vector<int32_t>& tie_owner, std::vector<int32_t>& ctl_owner);
 int image_order(const fba_problem* p, std::vector<int32_t>& order);   // checked camera_order
@@ -586,6 +599,19 @@ int launch_intersect(Ctx& c, const double* ray, const int32_t* rst, const double
 int launch_resect_gather(Ctx& c, bool use_all, double* rec, int32_t* use);
 int launch_resect(Ctx& c, const double* rec, const int32_t* use, int refine_iters, double min_ratio, double refine_tol,
                   bool write, double* eop, double* qual, int32_t* st);
+// data snooping (fba_snoop.hip), after launch_vce_q left q in d_q and v in d_res; every array in local order, the
+// image and point lists built.  SnoopBufs: the call's workspace.  launch_snoop_init: s0 = d_sw (1 without weights).
+// launch_snoop_round: the segments' active counts, W / W~ with the candidate and back-check flags, the segments'
+// winners, the picks into pick[image slot] and the round's counts into out [SNOOP_OUT].  launch_snoop_apply: mode 1
+// the picks become EXCLUDED, 2 the back-check's verdicts READMITTED, 0 neither; then d_sw = EPS s0 / s0 by state
+struct SnoopBufs {
+    double *s0 = nullptr, *W = nullptr, *part = nullptr, *out = nullptr;
+    uint8_t *state = nullptr, *cand = nullptr, *back = nullptr;
+    int32_t *win = nullptr, *cnt = nullptr, *pick = nullptr;
+};
+int launch_snoop_init(Ctx& c, const SnoopBufs& b);
+int launch_snoop_round(Ctx& c, const SnoopBufs& b, const double* d_q, int min_rays, int min_img_points, double crit);
+int launch_snoop_apply(Ctx& c, const SnoopBufs& b, int mode);
 int border_solve_selftest(int device, const double* gram, double* coef);  // fba_test_border_solve
 
 }  // namespace fba

@@ -858,6 +858,11 @@ void build_image_list(const std::vector<int32_t>& img, int n_img, std::vector<in
         if (img[o] >= 0 && img[o] < ni) list[(size_t)next[img[o]]++] = (int32_t)o;
 }
 
+// the same stable counting sort, keyed by the local tie point: a control observation (pt < 0) is in no list
+void build_point_list(const std::vector<int32_t>& pt, int n_lp, std::vector<int32_t>& start, std::vector<int32_t>& list) {
+    build_image_list(pt, n_lp, start, list);
+}
+
 int build_plan(const fba_problem* p, const fba_settings* s, const fba_options& opt, const fba_priors* pr,
                const PlanKnobs& knobs, Ctx& c, HostPlan& hp) {
     c.prob = *p;

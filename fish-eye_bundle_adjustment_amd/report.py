@@ -600,3 +600,49 @@ def read_wgt(path):
             w.append((float(c[3]), float(c[4])))
             flag.append(c[5] == "*")
     return rows, tgt, img, np.array(w, dtype=np.float64).reshape(-1, 2), np.array(flag, dtype=bool)
+
+
+SNOOP_STATE = ("ACTIVE", "EXCLUDED", "READMITTED")
+
+
+def write_snp(path, data, res):
+    """The data-snooping table <Output_Filename stem>.snp (no reference counterpart: main.m never tests a
+    measurement), tab-delimited in write_rsd's style, two parts.  Per image point the snooping excluded or re-admitted:
+    `E`, PHO row (1-based), image name, point name, the state word, W~ (an excluded point's statistic of the predicted
+    residual; W for a re-admitted one) of the last round, vx, vy in pixels.  Per round: `R`, round (1-based), points
+    picked, points the back-check passed, points excluded after the round, the largest W of an active point."""
+    if getattr(res, "snoop_excluded", None) is None or getattr(res, "snoop_table", None) is None:
+        raise ValueError("write_snp: the adjustment carries no data snooping (adjust(..., snoop=...))")
+    ex = np.asarray(res.snoop_excluded).reshape(-1)
+    stat = np.asarray(res.snoop_stat, dtype=np.float64).reshape(-1)
+    v = np.asarray(res.v, dtype=np.float64).reshape(-1, 2)
+    tab = np.asarray(res.snoop_table, dtype=np.float64).reshape(-1, 4)
+    if not (len(ex) == len(stat) == len(v) == len(data.pho_image)):
+        raise ValueError("write_snp: one state, statistic and residual pair per PHO row expected")
+    with open(path, "w") as fh:
+        for i in np.nonzero(ex)[0]:
+            fh.write("\t".join(["E", str(i + 1), str(data.pho_image[i]), str(data.pho_target[i]), SNOOP_STATE[int(ex[i])],
+                                _cell(stat[i]), _cell(v[i, 0]), _cell(v[i, 1])]) + "\n")
+        for k, row in enumerate(tab):
+            fh.write("\t".join(["R", str(k + 1), str(int(row[0])), str(int(row[1])), str(int(row[2])), _cell(row[3])]) + "\n")
+
+
+def read_snp(path):
+    """write_snp's table back: (rows (m) 0-based PHO rows, images (m), points (m), state words (m), stat (m), v (m, 2),
+    table (rounds, 4))"""
+    rows, imgs, pts, words, num, hist = [], [], [], [], [], []
+    with open(path) as fh:
+        for ln in fh:
+            c = ln.rstrip("\n").split("\t")
+            if c[0] == "E" and len(c) == 8:
+                rows.append(int(c[1]) - 1)
+                imgs.append(c[2])
+                pts.append(c[3])
+                words.append(c[4])
+                num.append([float(x) for x in c[5:8]])
+            elif c[0] == "R" and len(c) == 6:
+                hist.append([float(x) for x in c[2:6]])
+            else:
+                raise ValueError(f"read_snp: {path}: expected 8 tab-separated columns starting with E or 6 starting with R")
+    a = np.array(num, dtype=np.float64).reshape(-1, 3)
+    return (np.array(rows, dtype=np.int64), imgs, pts, words, a[:, 0], a[:, 1:], np.array(hist, dtype=np.float64).reshape(-1, 4))

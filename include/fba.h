@@ -569,6 +569,62 @@ int fba_vce_host(int64_t n_rows, int32_t n_groups, const int32_t* group, const d
                  const fba_vce_options* o, double* sums /*[n_groups+1][3]*/, double* sigma2, double* factor,
                  int32_t* status);
 
+/* Baarda data snooping over the image points (no reference counterpart: main.m never tests a measurement): the
+ * measurements whose w-test exceeds crit are eliminated and, once the adjustment is clean, re-checked -- on the device,
+ * from the reliability function's q and v (csrc/fba_snoop.h).  State is kept per image point (a PHO row: its x and y
+ * rows together): active, excluded -- both weights are 1e-12 x the starting weight, the weight setter's way of
+ * excluding a measurement -- or re-admitted.  One round:
+ *   1  Gauss-Newton steps from the device xhat while deltasum > Threshold_Value, at least one, at most Iteration_Cap;
+ *   2  the selected inverse and q = a Cx a' per row, as the reliability function forms it;
+ *   3  per active point W = max(|w_x|, |w_y|), r and w as the reliability function's (0 where r < 1e-10); per excluded
+ *      point the statistic of its predicted residual, W~ = max over its rows of |s0 v| / sqrt(sigma^2 + q / 1e-12), s0
+ *      the starting sqrt weight: a division, so a row whose r = 1 - 1e-12 x has lost x keeps its statistic;
+ *   4  candidates: the active points with W > crit whose removal leaves their tie point at least min_rays active
+ *      observations (a control observation has no tie point) and their image at least min_img_points, and that were
+ *      not re-admitted before (a re-admitted point is never a candidate again, so the rounds cannot cycle);
+ *   5  a candidate is eliminated when it has the largest W among the candidates of its tie point and among those of its
+ *      image, the lower PHO row between equal W: at most one per tie point and one per image in a round, so the
+ *      neighbours a gross error smears over wait for the next round, where they usually pass;
+ *   6  a round that eliminates nothing runs the back-check: every excluded point with W~ <= crit is re-admitted at
+ *      exactly its starting weights, the points the caller pre-excluded included.  Neither: converged;
+ *   7  otherwise the weights are changed and the next round begins.  The picks of the round max_rounds are found and
+ *      not applied (FBA_OK, *converged = 0); so are those that would take the excluded share past max_share of n_pts
+ *      (*converged = 0, bit 1 of *status_bits).
+ * Every solve of the call is followed by the selected inverse, which consumes its factor: afterwards xhat, the
+ * residuals function and the weight getter are those of the adjustment loop run with the final weights, and the
+ * post-fit outputs need one further step first, as after any other consumer of the factor.  Where nothing was changed
+ * (no candidate, or max_rounds = 1 without pre-excluded points) xhat and the weighting are bitwise those of fba_adjust.
+ *   excluded [n_pts], PHO order, in/out, may be NULL (all active): on entry nonzero = the point starts excluded (its
+ *   weights are lowered before round 1, also with max_rounds = 1); on exit 0 active, 1 excluded, 2 re-admitted.
+ *   stat [n_pts]: W or W~ of the last round.  table [max_rounds][4]: per round the points it picked, the points its
+ *   back-check passed, the points excluded after it, the largest W of an active point; rows of rounds not run are left
+ *   alone.  *rounds, *iterations (every Gauss-Newton step of the call), *converged.  Any output pointer may be NULL.
+ * Checked on the host before any GPU call, FBA_ERR_ARG: max_rounds, min_rays or min_img_points < 1, crit not finite or
+ * <= 0, max_share not in (0, 1], a call between the asynchronous solve and its finish.  FBA_ERR_UNSUPPORTED: world > 1,
+ * a robust loss, damping > 0 (the variance component function's refusals).  A refused call leaves the context untouched.
+ * Priors are never candidates.  The first change of an unweighted context switches its weights on (the accumulation
+ * graph is re-captured once); later rounds write in place.  Plain launches on the context's stream, no atomics: two
+ * calls on two fresh contexts are bitwise equal.  With fba_set_timing on, fba_last_timings' [7] afterwards holds the
+ * device time of the call's own kernels (the reliability part and the selection of every round, not the steps).
+ * fba_snoop_host (host only, no GPU): one round's selection (steps 4 - 7's stop) by the same routines in index order.
+ *   n points, W (or W~), state (0 / 1 / 2), tie (< 0: a control observation, else < n_tie), img (in [0, n_img)); the
+ *   PHO row of a point is its index and n_pts = n.  pick / readmit [n]: 1 where the round eliminates / re-admits;
+ *   *status_bits: bit 1 where the max_share stop cleared the picks. */
+typedef struct fba_snoop_options {
+    int32_t max_rounds;      /* >= 1; default (NULL options) 20; 1 = test only, nothing eliminated or re-admitted */
+    int32_t min_rays;        /* default 2: a tie point keeps at least this many active rays */
+    int32_t min_img_points;  /* default 6: the resection's minimum */
+    int32_t reserved;
+    double  crit;            /* default 3.29, the reliability table's flag line */
+    double  max_share;       /* default 0.05 of n_pts */
+} fba_snoop_options;
+int fba_snoop(fba_ctx* ctx, const fba_snoop_options* o, uint8_t* excluded /*[n_pts] PHO order, in/out; may be NULL*/,
+              double* stat /*[n_pts] W or W~ of the last round*/, double* table /*[max_rounds][4]*/, int32_t* rounds,
+              int32_t* iterations, int32_t* converged, int32_t* status_bits);
+int fba_snoop_host(int64_t n, const double* W, const uint8_t* state, const int32_t* tie, const int32_t* img,
+                   int32_t n_tie, int32_t n_img, const fba_snoop_options* o, uint8_t* pick /*[n]*/,
+                   uint8_t* readmit /*[n]*/, int32_t* status_bits);
+
 /* Per-phase device timings of the last fba_step / fba_accumulate+fba_solve_update, in ms:
  * [0] params+linearize, [1] point-side, [2] image/pair/camera accumulation, [3] border,
  * [4] Cholesky+forward, [5] backward+border solve, [6] back-substitution+update, [7] total. */
