@@ -132,6 +132,11 @@ class SnoopOptions(C.Structure):
         super().__init__(int(max_rounds), int(min_rays), int(min_img_points), 0, float(crit), float(max_share))
 
 
+def _given(**kw):
+    """the keywords a caller gave (not None): the *Options classes above hold the defaults of the others"""
+    return {k: v for k, v in kw.items() if v is not None}
+
+
 def pack_priors(priors):
     """(index, value, sigma) -> (fba_priors, the arrays it points into), or (None, None) for None / no rows.
     Shapes only: the values are checked by fba_create_priors, on the host, before it touches the GPU."""
@@ -516,21 +521,21 @@ class Context:
         check(lib.fba_image_rays(self.h, ptr(ray), ptr(st)))
         return ray[:n], st[:n]
 
-    def intersect(self, refine_iters=10, write_xhat=False, min_ratio=None, refine_tol=1e-10):
+    def intersect(self, refine_iters=None, write_xhat=None, min_ratio=None, refine_tol=None):
         """fba_intersect: (xyz, quality, status, n_not_ok) -- every tie point intersected from its image rays at the
         device xhat, TIE order: xyz (n_tie, 3); quality (n_tie, 4): rays used, lambda_min / lambda_max of the
         intersection's normal matrix, RMS reprojection residual (px) of the linear and of the refined solution;
         status (n_tie) FBA_ISECT_* (capi.ISECT_STATUS); the number of points not OK.  write_xhat: the OK and REFINE
         points replace their entries of the device xhat.  Other ranks' tie points are 0."""
         nt = self.packed.n_tie
-        op = IntersectOptions(refine_iters, write_xhat, refine_tol=refine_tol) if min_ratio is None else \
-            IntersectOptions(refine_iters, write_xhat, min_ratio, refine_tol)
+        op = IntersectOptions(**_given(refine_iters=refine_iters, write_xhat=write_xhat, min_ratio=min_ratio,
+                                       refine_tol=refine_tol))
         xyz, q, st = np.zeros((max(nt, 1), 3)), np.zeros((max(nt, 1), 4)), np.zeros(max(nt, 1), dtype=np.int32)
         bad = C.c_int64()
         check(lib.fba_intersect(self.h, C.byref(op), ptr(xyz), ptr(q), ptr(st), C.byref(bad)))
         return xyz[:nt], q[:nt], st[:nt], bad.value
 
-    def resect(self, use="control", refine_iters=10, write_xhat=False, min_ratio=1e-6, refine_tol=1e-10):
+    def resect(self, use=None, refine_iters=None, write_xhat=None, min_ratio=None, refine_tol=None):
         """fba_resect: (eop, quality, status, n_not_ok) -- every image resected from object points and its measured
         image rays at the device xhat, EXT order: eop (n_img, 6) Xc Yc Zc omega phi kappa; quality (n_img, 5): points
         used, lambda_1 / lambda_11 of the linear solution's Gram matrix, RMS reprojection residual (px) of the linear
@@ -539,13 +544,14 @@ class Context:
         or "all" (also the tie observations at the device xhat's tie coordinates).  write_xhat: the OK and REFINE
         images replace their six entries of the device xhat.  One GPU only (world == 1)."""
         ni = self.packed.n_img
-        op = ResectOptions(use, refine_iters, write_xhat, min_ratio, refine_tol)
+        op = ResectOptions(**_given(use=use, refine_iters=refine_iters, write_xhat=write_xhat, min_ratio=min_ratio,
+                                    refine_tol=refine_tol))
         eop, q, st = np.zeros((max(ni, 1), 6)), np.zeros((max(ni, 1), 5)), np.zeros(max(ni, 1), dtype=np.int32)
         bad = C.c_int64()
         check(lib.fba_resect(self.h, C.byref(op), ptr(eop), ptr(q), ptr(st), C.byref(bad)))
         return eop[:ni], q[:ni], st[:ni], bad.value
 
-    def vce(self, group, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0, clip=100.0):
+    def vce(self, group, n_groups, max_rounds=None, tol=None, min_redundancy=None, clip=None):
         """fba_vce: variance components of groups of image measurements, estimated and applied on the device.
         group: (2 n_pts) ids in [0, n_groups) or -1 (no estimated group), PHO order, x y interleaved like v (or
         (n_pts, 2)).  Returns a dict: component (n_groups + 2) the cumulative variance factor of each group relative to
@@ -557,10 +563,10 @@ class Context:
         g = np.ascontiguousarray(group, dtype=np.int32).reshape(-1)
         if g.size != 2 * self.packed.n_pts:
             raise ValueError("vce: group must have 2*n_pts entries")
-        op = VceOptions(max_rounds, tol, min_redundancy, clip)
+        op = VceOptions(**_given(max_rounds=max_rounds, tol=tol, min_redundancy=min_redundancy, clip=clip))
         ng2 = max(int(n_groups), 0) + 2
         comp = np.zeros(ng2)
-        table = np.zeros((max(int(max_rounds), 1), ng2, 4))
+        table = np.zeros((max(op.max_rounds, 1), ng2, 4))
         st = np.zeros(ng2, dtype=np.int32)
         rounds, its, conv = C.c_int32(), C.c_int32(), C.c_int32()
         check(lib.fba_vce(self.h, int(n_groups), ptr(g), C.byref(op), ptr(comp), ptr(table), ptr(st), C.byref(rounds),
@@ -568,7 +574,7 @@ class Context:
         return {"component": comp, "table": table[: rounds.value].copy(), "status": st, "rounds": rounds.value,
                 "iterations": its.value, "converged": bool(conv.value)}
 
-    def snoop(self, excluded=None, max_rounds=20, min_rays=2, min_img_points=6, crit=3.29, max_share=0.05):
+    def snoop(self, excluded=None, max_rounds=None, min_rays=None, min_img_points=None, crit=None, max_share=None):
         """fba_snoop: Baarda data snooping over the image points on the device -- rounds of adjustment, w-test,
         elimination of the local maxima above crit (at most one per tie point and per image in a round) and, once a
         round eliminates nothing, re-admission of the excluded points whose predicted residual passes the test.
@@ -585,9 +591,10 @@ class Context:
             if e.size != n:
                 raise ValueError("snoop: excluded must have n_pts entries")
             ex[:n] = e != 0
-        op = SnoopOptions(max_rounds, min_rays, min_img_points, crit, max_share)
+        op = SnoopOptions(**_given(max_rounds=max_rounds, min_rays=min_rays, min_img_points=min_img_points, crit=crit,
+                                   max_share=max_share))
         stat = np.zeros(max(n, 1))
-        table = np.zeros((max(int(max_rounds), 1), 4))
+        table = np.zeros((max(op.max_rounds, 1), 4))
         rounds, its, conv, bits = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         check(lib.fba_snoop(self.h, C.byref(op), ptr(ex), ptr(stat), ptr(table), C.byref(rounds), C.byref(its),
                             C.byref(conv), C.byref(bits)))
@@ -644,8 +651,8 @@ def unproject_host(typ, xy, camtab):
     return out[: len(xy)], st[: len(xy)]
 
 
-def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, refine_iters=10, min_ratio=1e-6,
-                refine_tol=1e-10):
+def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, refine_iters=None, min_ratio=None,
+                refine_tol=None):
     """fba_resect_host: the device's per-image resection (csrc/fba_resect.h) run on the CPU for one image, no GPU
     needed.  typ: a name of TYPES or the FBA_TYPE_* number; xyz (n, 3) object points; ray (n, 5) unproject_host's
     rows of their measurements; ray_status (n) FBA_RAY_* or None; c, ydir of the camera -> (eop (6), quality (5),
@@ -658,7 +665,7 @@ def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, r
     rs = None if ray_status is None else np.ascontiguousarray(ray_status, dtype=np.int32).reshape(-1)
     if rs is not None and len(rs) != len(xyz):
         raise ValueError("resect_host: one ray status per object point expected")
-    op = ResectOptions("control", refine_iters, False, min_ratio, refine_tol)
+    op = ResectOptions(**_given(refine_iters=refine_iters, min_ratio=min_ratio, refine_tol=refine_tol))
     eop, q, st = np.zeros(6), np.zeros(5), C.c_int32()
     n = len(xyz)
     check(lib.fba_resect_host(t, n, ptr(xyz) if n else None, ptr(ray) if n else None, ptr(rs) if (rs is not None and n) else None,
@@ -667,7 +674,7 @@ def resect_host(typ, xyz, ray, c, ydir, ray_status=None, std_x=0.3, std_y=0.3, r
     return eop, q, st.value
 
 
-def vce_host(group, r, t, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0, clip=100.0):
+def vce_host(group, r, t, n_groups, max_rounds=None, tol=None, min_redundancy=None, clip=None):
     """fba_vce_host: the device's group arithmetic (csrc/fba_vce.h) run on the CPU, no GPU needed: the sums of r and t
     over the rows of each group in index order, then the estimate, the clamp, the factor and the status.  group (n)
     ids in [0, n_groups) or -1 -> (sums (n_groups + 1, 3): R T n, the last row the ids -1; sigma2, factor, status
@@ -677,7 +684,7 @@ def vce_host(group, r, t, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0,
     t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
     if not (g.size == r.size == t.size):
         raise ValueError("vce_host: group, r and t must have the same length")
-    op = VceOptions(max_rounds, tol, min_redundancy, clip)
+    op = VceOptions(**_given(max_rounds=max_rounds, tol=tol, min_redundancy=min_redundancy, clip=clip))
     ng = max(int(n_groups), 0)
     sums, s2, f, st = np.zeros((ng + 1, 3)), np.zeros(max(ng, 1)), np.zeros(max(ng, 1)), np.zeros(max(ng, 1), dtype=np.int32)
     n = g.size
@@ -686,8 +693,8 @@ def vce_host(group, r, t, n_groups, max_rounds=10, tol=1e-3, min_redundancy=1.0,
     return sums, s2[:ng], f[:ng], st[:ng]
 
 
-def snoop_host(W, state, tie, img, n_tie=None, n_img=None, max_rounds=20, min_rays=2, min_img_points=6, crit=3.29,
-               max_share=0.05):
+def snoop_host(W, state, tie, img, n_tie=None, n_img=None, max_rounds=None, min_rays=None, min_img_points=None, crit=None,
+               max_share=None):
     """fba_snoop_host: one round's selection of the data snooping (csrc/fba_snoop.h) run on the CPU in index order, no
     GPU needed.  W (n) the points' statistics, state (n) 0 active / 1 excluded / 2 re-admitted, tie (n) the tie point
     (< 0: a control observation), img (n) the image -> (pick, readmit (n) bool, status_bits)."""
@@ -700,7 +707,8 @@ def snoop_host(W, state, tie, img, n_tie=None, n_img=None, max_rounds=20, min_ra
         raise ValueError("snoop_host: W, state, tie and img must have the same length")
     n_tie = int(tie.max(initial=-1)) + 1 if n_tie is None else int(n_tie)
     n_img = int(img.max(initial=-1)) + 1 if n_img is None else int(n_img)
-    op = SnoopOptions(max_rounds, min_rays, min_img_points, crit, max_share)
+    op = SnoopOptions(**_given(max_rounds=max_rounds, min_rays=min_rays, min_img_points=min_img_points, crit=crit,
+                               max_share=max_share))
     pick, back = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
     bits = C.c_int32()
     z = lambda a: ptr(a) if n else None

@@ -385,6 +385,11 @@ struct Ctx {
     bool have_delta = false;
     bool have_factor = false;    // d_S holds the factor of the last solve (fba_covariance consumes it)
     bool pending = false;        // fba_solve_update_async enqueued, fba_solve_finish not yet called
+    // Outside the step itself (accumulate, solve_finish) these two are what clears have_lin / have_delta / have_factor:
+    // after a change of the device xhat neither the linearisation, the correction nor the factor is this xhat's;
+    // after a change of the weighting (weights, loss, damping) neither the linearisation nor the factor is its
+    void xhat_changed() { have_lin = have_delta = have_factor = false; }
+    void weights_changed() { have_lin = have_factor = false; }
     std::vector<int32_t> ref_img_cam;  // [n_img_ref] camera of each EXT image (-1: no observation)
     int iterations = 0;
     bool timing = false;

@@ -21,11 +21,6 @@
 
 #include "../fish-eye_bundle_adjustment_amd/csrc/fba_internal.h"
 
-namespace fba {
-static std::string g_err;
-void set_error(const std::string& msg) { g_err = msg; }
-}  // namespace fba
-
 using namespace fba;
 
 static int fail_at(const char* what, int line) {
@@ -113,12 +108,12 @@ static int check_rank(const Scene& sc, int world, int rank, int split, double ra
     fba_priors prs{(int64_t)sc.pr_index.size(), sc.pr_index.data(), pval.data(), psig.data()};
     const fba_priors* pr = &prs;
     fba_options opt{};
-    if (check_inputs(&p, &set, &o, &pr, opt)) return fail_at(g_err.c_str(), __LINE__);
+    if (check_inputs(&p, &set, &o, &pr, opt)) return fail_at(fba_last_error(), __LINE__);
     Ctx c;
     HostPlan hp;
     PlanKnobs knobs;
     knobs.pair_terms = ratio;
-    if (build_plan(&p, &set, opt, pr, knobs, c, hp)) return fail_at(g_err.c_str(), __LINE__);
+    if (build_plan(&p, &set, opt, pr, knobs, c, hp)) return fail_at(fba_last_error(), __LINE__);
     CHECK(c.sched.split == (split != 0));
 
     const Layout& L = c.L;

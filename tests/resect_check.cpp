@@ -1,14 +1,17 @@
 // resect_check.cpp -- stand-alone checker of the space resection's host-visible routines (tests/test_resect_host.py
-// builds it with -Xarch_host -fsanitize=address,undefined -- the host compilation only -- and runs it directly; no GPU,
-// no HIP call).
+// builds it with -Xarch_host -fsanitize=address,undefined -- the host compilation only -- together with
+// fba_api_host.cpp / fba_plan.cpp / fba_order.cpp and runs it directly; no GPU, no HIP call).
 //
 // Drives csrc/fba_resect.h's per-image routines through the host's source of sums over the edge cases -- exact data of
 // every Type and both sides of W, 0 / 5 / 6 points, coplanar points, a NaN point, every usable flag off, phi at a right
 // angle, a singular 6 x 6 system -- and fba_plan.cpp's image-list builder: an image without observations, an empty
-// problem, no images, slots out of range.  One "ok <case>" line per case; any failure prints "FAIL ..." and exits 1.
+// problem, no images, slots out of range.  Every case also goes through the exported fba_resect_host, which must give
+// the same numbers; then one refusal per argument check of it.  One "ok <case>" line per case; any failure prints
+// "FAIL ..." and exits 1.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <random>
 #include <vector>
@@ -17,10 +20,6 @@
 #include "../fish-eye_bundle_adjustment_amd/csrc/fba_resect.h"
 
 using namespace fba;
-
-namespace fba {
-void set_error(const std::string& msg) { std::printf("error: %s\n", msg.c_str()); }  // the planner's error sink
-}  // namespace fba
 
 #define CHECK(cond)                                                     \
     do {                                                                \
@@ -67,8 +66,26 @@ static Result solve(int type, const Scene& s, int64_t n, const int32_t* use, int
     const double cur[6] = {1, 2, 3, 4, 5, 6};
     Result r;
     resect_solve(src, type, 1.0 / 0.09, 1.0 / 0.09, iters, 1e-6, 1e-10, A.data(), V.data(), cur, r.eop, r.qual, r.status);
+    // the exported entry point on the same records, from and into arrays of exactly the documented sizes: the same
+    // status and quality, and the same pose where there is one (FEW and WEAK: zeros, where the routine keeps `cur`)
+    std::vector<double> xyz(3 * (size_t)n), ray(5 * (size_t)n), eop(6), qual(5);
+    std::vector<int32_t> rst((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        for (int q = 0; q < 5; ++q) ray[5 * i + q] = s.rec[RESECT_REC * i + q];
+        for (int q = 0; q < 3; ++q) xyz[3 * i + q] = s.rec[RESECT_REC * i + 5 + q];
+        rst[(size_t)i] = (!use || use[i]) ? FBA_RAY_OK : FBA_RAY_DOMAIN;
+    }
+    const fba_resect_options op{FBA_RESECT_USE_CONTROL, iters, 0, 0, 1e-6, 1e-10};
+    int32_t st = -1;
+    CHECK(fba_resect_host(type, n, xyz.data(), ray.data(), use ? rst.data() : nullptr, s.c, s.ydir, 0.3, 0.3, &op, eop.data(),
+                          qual.data(), &st) == FBA_OK);
+    const bool pose = r.status == FBA_RESECT_OK || r.status == FBA_RESECT_REFINE;
+    CHECK(st == r.status && !std::memcmp(qual.data(), r.qual, sizeof r.qual));
+    for (int q = 0; q < 6; ++q) CHECK(pose ? eop[q] == r.eop[q] : eop[q] == 0.0);
     return r;
 }
+
+static bool refused(int rc, int code, const char* text) { return rc == code && !std::strcmp(fba_last_error(), text); }
 
 static double centre_error(const Result& r, const Scene& s) {
     double e = 0.0;
@@ -181,5 +198,27 @@ int main() {
         CHECK(r.status != FBA_RESECT_FEW && r.qual[0] == 7.0);
     }
     std::printf("ok tail\n");
+    {  // fba_resect_host: one refusal per argument check; every output optional, the defaults of a NULL options pointer
+        const Scene s = make_scene(FBA_TYPE_FISHEYE, 6, eop, -1.0, false, 17u);
+        std::vector<double> xyz(18), ray(30);
+        for (int i = 0; i < 6; ++i) {
+            for (int q = 0; q < 5; ++q) ray[5 * i + q] = s.rec[RESECT_REC * i + q];
+            for (int q = 0; q < 3; ++q) xyz[3 * i + q] = s.rec[RESECT_REC * i + 5 + q];
+        }
+        auto call = [&](int type, int64_t n, const double* X, double sx, const fba_resect_options* o) {
+            return fba_resect_host(type, n, X, ray.data(), nullptr, s.c, s.ydir, sx, 0.3, o, nullptr, nullptr, nullptr);
+        };
+        CHECK(refused(call(9, 6, xyz.data(), 0.3, nullptr), FBA_ERR_TYPE, "fba_resect_host: invalid type"));
+        const char* args = "fba_resect_host: n >= 0, xyz and ray not NULL, the standard deviations > 0";
+        CHECK(refused(call(FBA_TYPE_FISHEYE, -1, xyz.data(), 0.3, nullptr), FBA_ERR_ARG, args));
+        CHECK(refused(call(FBA_TYPE_FISHEYE, 6, nullptr, 0.3, nullptr), FBA_ERR_ARG, args));
+        CHECK(refused(call(FBA_TYPE_FISHEYE, 6, xyz.data(), 0.0, nullptr), FBA_ERR_ARG, args));
+        const fba_resect_options bad{FBA_RESECT_USE_CONTROL, -1, 0, 0, 1e-6, 1e-10};
+        CHECK(refused(call(FBA_TYPE_FISHEYE, 6, xyz.data(), 0.3, &bad), FBA_ERR_ARG,
+                      "fba_resect_host: use CONTROL or ALL, refine_iters >= 0, min_ratio and refine_tol finite and >= 0"));
+        CHECK(call(FBA_TYPE_FISHEYE, 6, xyz.data(), 0.3, nullptr) == FBA_OK);
+        CHECK(call(FBA_TYPE_FISHEYE, 0, nullptr, 0.3, nullptr) == FBA_OK);
+    }
+    std::printf("ok entry point\n");
     return 0;
 }

@@ -1,24 +1,24 @@
 // snoop_check.cpp -- stand-alone checker of the data-snooping arithmetic and selection the device and the host share,
 // and of the point list builder (tests/test_snoop_host.py builds it with -Xarch_host -fsanitize=address,undefined --
-// the host compilation only -- together with fba_plan.cpp / fba_order.cpp and runs it directly; no GPU, no HIP call).
+// the host compilation only -- together with fba_api_host.cpp / fba_plan.cpp / fba_order.cpp and runs it directly; no
+// GPU, no HIP call).
 //
 // Drives csrc/fba_snoop.h's routines over the edge cases: the two statistics, no candidates, equal W (the lower row
 // wins), a two-ray tie point, an image at min_img_points, the local-maximum rule, the back-check, a re-admitted
 // point, the max_share stop, empty lists; and build_point_list over a tie point without observations, control
-// observations and an empty problem.  One "ok <case>" line per case; any failure prints "FAIL ..." and exits 1.
+// observations and an empty problem.  Every selection in index order also goes through the exported fba_snoop_host,
+// which must give the same flags; then its max_share stop and one refusal per argument check.  One "ok <case>" line
+// per case; any failure prints "FAIL ..." and exits 1.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <vector>
 
 #include "../fish-eye_bundle_adjustment_amd/csrc/fba_internal.h"
 #include "../fish-eye_bundle_adjustment_amd/csrc/fba_snoop.h"
-
-namespace fba {
-void set_error(const std::string&) {}
-}  // namespace fba
 
 using namespace fba;
 
@@ -43,8 +43,18 @@ static Sel run(const std::vector<double>& W, const std::vector<uint8_t>& st, con
     s.back.resize(W.size());
     snoop_select((int64_t)W.size(), W.data(), st.data(), tie.data(), img.data(), row ? row->data() : nullptr, n_tie, n_img,
                  min_rays, min_img, crit, s.pick.data(), s.back.data(), s.n_pick, s.n_back);
+    if (!row) {  // the exported entry point in index order, into arrays of exactly the documented sizes: the same flags
+        std::vector<uint8_t> pick(W.size()), back(W.size());
+        const fba_snoop_options op{20, min_rays, min_img, 0, crit, 1.0};
+        int32_t bits = -1;
+        CHECK(fba_snoop_host((int64_t)W.size(), W.data(), st.data(), tie.data(), img.data(), n_tie, n_img, &op, pick.data(),
+                             back.data(), &bits) == FBA_OK);
+        CHECK(pick == s.pick && back == s.back && bits == 0);
+    }
     return s;
 }
+
+static bool refused(int rc, const char* text) { return rc == FBA_ERR_ARG && !std::strcmp(fba_last_error(), text); }
 
 int main() {
     {  // the statistics: r = 0.5 -> w = s v / (sigma sqrt(r)); r < 1e-10 -> 0; the excluded row by division
@@ -121,6 +131,27 @@ int main() {
         build_point_list({0, 7}, 2, start, list);  // an index past n_lp is left out (fba_snoop refuses it before)
         CHECK((start == std::vector<int32_t>{0, 1, 1}) && (list == std::vector<int32_t>{0}));
         std::printf("ok point list\n");
+    }
+    {  // fba_snoop_host: the max_share stop clears the picks, the defaults of a NULL options pointer, one refusal per
+       // argument check
+        const std::vector<double> W{9, 5, 1, 8, 1, 4};
+        std::vector<uint8_t> pick(6), back(6);
+        int32_t bits = 0;
+        const fba_snoop_options one{20, 2, 1, 0, 3.29, 0.1};  // 1 of 6 points is more than a tenth
+        CHECK(fba_snoop_host(6, W.data(), act.data(), tie.data(), img.data(), 2, 3, &one, pick.data(), back.data(), &bits) == FBA_OK);
+        CHECK(bits == 2 && pick == std::vector<uint8_t>(6, 0));
+        CHECK(fba_snoop_host(6, W.data(), act.data(), tie.data(), img.data(), 2, 3, nullptr, pick.data(), back.data(), nullptr) == FBA_OK);
+        CHECK(pick == std::vector<uint8_t>(6, 0));  // min_img_points 6: no image can give a point
+        const fba_snoop_options bad{20, 0, 6, 0, 3.29, 0.05};
+        CHECK(refused(fba_snoop_host(6, W.data(), act.data(), tie.data(), img.data(), 2, 3, &bad, pick.data(), back.data(), &bits),
+                      "fba_snoop_host: max_rounds, min_rays and min_img_points >= 1; crit > 0 and 0 < max_share <= 1, both finite"));
+        CHECK(refused(fba_snoop_host(6, W.data(), act.data(), tie.data(), img.data(), 2, 3, nullptr, nullptr, back.data(), &bits),
+                      "fba_snoop_host: n, n_tie, n_img >= 0 and no NULL array"));
+        CHECK(refused(fba_snoop_host(-1, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr),
+                      "fba_snoop_host: n, n_tie, n_img >= 0 and no NULL array"));
+        CHECK(refused(fba_snoop_host(6, W.data(), act.data(), tie.data(), img.data(), 2, 2, nullptr, pick.data(), back.data(), &bits),
+                      "fba_snoop_host: point 2: tie 0 (< 2), img 2 (in [0, 2)), state 0 (0, 1 or 2)"));
+        std::printf("ok entry point\n");
     }
     return 0;
 }

@@ -19,7 +19,8 @@ CSRC = os.path.join(ROOT, "fish-eye_bundle_adjustment_amd", "csrc")
 def checker(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("plan") / "plan_check")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "plan_check.cpp"),
-                    os.path.join(CSRC, "fba_plan.cpp"), os.path.join(CSRC, "fba_order.cpp"), "-o", exe], check=True)
+                    os.path.join(CSRC, "fba_api_host.cpp"), os.path.join(CSRC, "fba_plan.cpp"), os.path.join(CSRC, "fba_order.cpp"),
+                    "-o", exe], check=True)
     return exe
 
 

@@ -144,7 +144,8 @@ def test_sanitizer_program(tmp_path):
     # host code only: each sanitizer option applies to the host compilation (-Xarch_host), none to a device pass
     subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
                     "-Xarch_host", "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "snoop_check.cpp"),
-                    os.path.join(CSRC, "fba_plan.cpp"), os.path.join(CSRC, "fba_order.cpp"), "-o", exe], check=True)
+                    os.path.join(CSRC, "fba_api_host.cpp"), os.path.join(CSRC, "fba_plan.cpp"), os.path.join(CSRC, "fba_order.cpp"),
+                    "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     lines = r.stdout.splitlines()
     assert r.returncode == 0 and lines and all(ln.startswith("ok ") for ln in lines), r.stdout + r.stderr

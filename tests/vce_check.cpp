@@ -1,16 +1,20 @@
 // vce_check.cpp -- stand-alone checker of the variance-component arithmetic the device and the host share
 // (tests/test_vce_host.py builds it with -Xarch_host -fsanitize=address,undefined -- the host compilation only -- and
-// runs it directly; no GPU, no HIP call).
+// runs it directly, linked with csrc/fba_api_host.cpp, fba_plan.cpp and fba_order.cpp; no GPU, no HIP call).
 //
 // Drives csrc/fba_vce.h's row, sum and group routines over the edge cases: an empty group, every id -1, R below
 // min_redundancy, T = 0 (CLIPPED at 1 / clip), an estimate above clip, a NaN row, n_groups 1 and 256, an empty
-// problem, ids out of range.  One "ok <case>" line per case; any failure prints "FAIL ..." and exits 1.
+// problem, ids out of range -- and, on every case whose ids it accepts, the exported fba_vce_host, which must give
+// the same numbers; then one refusal per argument check of fba_vce_host.  One "ok <case>" line per case; any failure
+// prints "FAIL ..." and exits 1.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <vector>
 
+#include "../include/fba.h"
 #include "../fish-eye_bundle_adjustment_amd/csrc/fba_vce.h"
 
 using namespace fba;
@@ -38,8 +42,27 @@ static Out run(int n_groups, const std::vector<int32_t>& g, const std::vector<do
     vce_sum_rows((int64_t)g.size(), n_groups, g.data(), r.data(), t.data(), o.sums.data());
     for (int i = 0; i < n_groups; ++i)
         vce_group(o.sums[3 * i], o.sums[3 * i + 1], o.sums[3 * i + 2], min_red, clip, o.sigma2[i], o.factor[i], o.status[i]);
+    bool valid = true, finite = true;
+    for (int32_t id : g) valid = valid && id >= -1 && id < n_groups;
+    for (int i = 0; i <= n_groups; ++i) finite = finite && std::isfinite(o.sums[3 * i]) && std::isfinite(o.sums[3 * i + 1]);
+    if (valid) {  // the exported entry point on the same rows, into arrays of exactly the documented sizes: the same bits
+        Out h;
+        h.sums.resize(o.sums.size());
+        h.sigma2.resize(n_groups);
+        h.factor.resize(n_groups);
+        h.status.resize(n_groups);
+        const fba_vce_options op{10, 0, 1e-3, min_red, clip};
+        const int rc = fba_vce_host((int64_t)g.size(), n_groups, g.data(), r.data(), t.data(), &op, h.sums.data(), h.sigma2.data(),
+                                    h.factor.data(), h.status.data());
+        CHECK(rc == (finite ? FBA_OK : FBA_ERR_NONFINITE));
+        CHECK(!std::memcmp(h.sums.data(), o.sums.data(), sizeof(double) * o.sums.size()));
+        CHECK(!std::memcmp(h.sigma2.data(), o.sigma2.data(), sizeof(double) * n_groups));
+        CHECK(!std::memcmp(h.factor.data(), o.factor.data(), sizeof(double) * n_groups) && h.status == o.status);
+    }
     return o;
 }
+
+static bool refused(int rc, const char* text) { return rc == FBA_ERR_ARG && !std::strcmp(fba_last_error(), text); }
 
 int main() {
     {  // the row quantities
@@ -98,6 +121,23 @@ int main() {
         const Out b = run(FBA_VCE_MAX_GROUPS, g, r, t);
         for (int i = 0; i < FBA_VCE_MAX_GROUPS; ++i) CHECK(b.status[i] == FBA_VCE_OK && b.sigma2[i] == 2.0 && b.sums[3 * i + 2] == 3.0);
         std::printf("ok sizes\n");
+    }
+    {  // fba_vce_host: one refusal per argument check, and the defaults of a NULL options pointer
+        const int32_t g[2] = {0, 1}, far[2] = {0, 2};
+        const double r[2] = {1.0, 1.0};
+        std::vector<double> sums(9), s2(2), f(2);
+        std::vector<int32_t> st(2);
+        CHECK(refused(fba_vce_host(2, 0, g, r, r, nullptr, nullptr, nullptr, nullptr, nullptr), "fba_vce_host: n_groups = 0 outside [1, 256]"));
+        const fba_vce_options bad{0, 0, 1e-3, 1.0, 100.0};
+        CHECK(refused(fba_vce_host(2, 2, g, r, r, &bad, nullptr, nullptr, nullptr, nullptr),
+                      "fba_vce_host: max_rounds >= 1; tol >= 0, min_redundancy >= 0 and clip >= 1, all finite"));
+        CHECK(refused(fba_vce_host(2, 2, nullptr, r, r, nullptr, nullptr, nullptr, nullptr, nullptr), "fba_vce_host: NULL group array"));
+        CHECK(refused(fba_vce_host(2, 2, far, r, r, nullptr, nullptr, nullptr, nullptr, nullptr), "fba_vce_host: group[1] = 2 outside [-1, 2)"));
+        CHECK(refused(fba_vce_host(2, 2, g, r, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "fba_vce_host: NULL r or t"));
+        CHECK(fba_vce_host(2, 2, g, r, r, nullptr, sums.data(), s2.data(), f.data(), st.data()) == FBA_OK);
+        CHECK(st[0] == FBA_VCE_OK && s2[1] == 1.0 && sums[2] == 1.0 && sums[8] == 0.0);
+        CHECK(fba_vce_host(2, 2, g, r, r, nullptr, nullptr, nullptr, nullptr, nullptr) == FBA_OK);  // every output optional
+        std::printf("ok entry point\n");
     }
     return 0;
 }
